@@ -15,6 +15,11 @@ and a step probes every piece and ORs the verdict bitmaps onto each read
 set's owner (RCCL across ranks).  The device-routed step (routing +
 exchange inside the timed region) is reported beside it.
 
+A plain run sets up, warms up, times --steps steps and prints the result
+line; --dump-outputs DIR also writes the last timed step's verdicts.  --full
+adds every other leg (CPU baselines and parity, PMC traffic, the drop-in
+entry, the one-stream and cache-resident legs, per-kernel times).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -48,6 +53,18 @@ def probe_struct(hsc, b, verdict, bitmap, T):
                           b["lock_table"].data_ptr(), b["lock_snap"].data_ptr(),
                           b["lock_txn"].data_ptr(), T, verdict.data_ptr(),
                           bitmap.data_ptr() if bitmap is not None else None)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: each array as DIR/<name>.npy in float32, 64 MB in
+    all at the most (of a larger array a fixed, seeded sample in index order)."""
+    os.makedirs(d, exist_ok=True)
+    cap = (64 << 20) // 4 // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0xC0FFEE).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_model():
@@ -290,14 +307,17 @@ def bench_commit_stream(args):
     if os.path.exists(gpath) and args.n_txn_c1 == 10_000:
         parity = json.load(open(gpath))["rc"] == rcs
     native = tc.sum() + ta.sum()
-    fb, rb = _commit_stream_fold_leg(ev, 1000, True)
-    fi, ri = _commit_stream_fold_leg(ev, 1000, False)
-    fb["parity_with_oracle_golden"] = parity is not None and rb == rcs and parity
-    fi["parity_with_oracle_golden"] = parity is not None and ri == rcs and parity
-    golden = json.load(open(gpath))["rc"] if os.path.exists(gpath) and args.n_txn_c1 == 10_000 else None
-    protocol = _protocol_leg(args, golden)
+    folds = protocol = None
+    if args.full:
+        fb, rb = _commit_stream_fold_leg(ev, 1000, True)
+        fi, ri = _commit_stream_fold_leg(ev, 1000, False)
+        fb["parity_with_oracle_golden"] = parity is not None and rb == rcs and parity
+        fi["parity_with_oracle_golden"] = parity is not None and ri == rcs and parity
+        folds = {"background": fb, "inline": fi}
+        golden = json.load(open(gpath))["rc"] if os.path.exists(gpath) and args.n_txn_c1 == 10_000 else None
+        protocol = _protocol_leg(args, golden)
     steady = None
-    if args.c1_steady:
+    if args.full and args.c1_steady:
         ev2 = config1_events(seed=SEED_CONFIG1 + 1, n_txn=args.c1_steady)
         sb, rsb = _commit_stream_fold_leg(ev2, 0, True)      # default threshold, background
         si, rsi = _commit_stream_fold_leg(ev2, 32768, False)  # the same threshold, inline
@@ -320,7 +340,7 @@ def bench_commit_stream(args):
            "check_us": _pct(tc), "append_us_per_commit": _pct(ta),
            "stream_wall_s": wall, "parity_with_oracle_golden": parity,
            "cpu_baseline": None if args.no_cpu else commit_stream_cpu_baseline(args),
-           "fold_every_1k_commits": {"background": fb, "inline": fi},
+           "fold_every_1k_commits": folds,
            "commit_protocol": protocol,
            "steady_state": steady,
            "note": "value = commits / (time inside the native check and append calls: "
@@ -1425,6 +1445,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the rocprofv3 traffic "
+                         "passes, the CPU baselines and their parity checks, the drop-in entry "
+                         "legs, the one-stream / cache-resident legs, per-kernel times and the "
+                         "window rebuild (config 1: the fold, protocol and steady-state legs). "
+                         "Without it a run sets up, warms up, times --steps steps and prints "
+                         "the result line; --no-cpu / --no-pmc / --no-api trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one-GPU configs 2 / 3 / 5: after the timed steps write what the last "
+                         "timed step computed (its verdict bytes, one per read set) as "
+                         "DIR/verdict.npy (float32)")
     ap.add_argument("--batches", type=int, default=2,
                     help="distinct resident read-set batches (at least; see --ring-gb)")
     ap.add_argument("--ring-gb", type=float, default=None,
@@ -1496,6 +1527,11 @@ def main():
         args.streams = 3 if args.config == 3 else 2
     if args.ring_gb is None:
         args.ring_gb = 1.1 if args.config in (2, 3, 5) else 0.0
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu = args.no_pmc = args.no_api = True
+    if args.dump_outputs and (args.config in (1, 4) or args.gpus > 1 or args.inproc > 1
+                              or args.rank_path or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs: one-GPU runs of configs 2, 3 and 5 only")
 
     if args.config == 4:
         return bench_graph(args)
@@ -1596,9 +1632,11 @@ def main():
     tl = torch.from_numpy(lsn.view(np.int64)).to(dev)
     v.ingest_device(n_w, words.shape[0], tg.data_ptr(), tw.data_ptr(), tl.data_ptr(), end_lsn)
     ingest_cold_ms = v.timing()["ingest_ms"]  # first build: its buffers are allocated inside
-    # the same rows again: a rebuild over allocated buffers (a fold, a re-ingest)
-    v.ingest_device(n_w, words.shape[0], tg.data_ptr(), tw.data_ptr(), tl.data_ptr(), end_lsn)
-    ingest_ms = v.timing()["ingest_ms"]
+    ingest_ms = None
+    if args.full:
+        # the same rows again: a rebuild over allocated buffers (a fold, a re-ingest)
+        v.ingest_device(n_w, words.shape[0], tg.data_ptr(), tw.data_ptr(), tl.data_ptr(), end_lsn)
+        ingest_ms = v.timing()["ingest_ms"]
     del tg, tw, tl
     if c3 is not None:
         v.merge_table_max(c3.table_max)  # data-row writes lock tables too
@@ -1658,14 +1696,20 @@ def main():
     # the ring: every timed step probes a batch no other step of the region touches
     # (warmup + steps <= NB) or, with a longer run, the least recently probed one
     elapsed = timed(S, NB)
+    if args.dump_outputs:
+        # the last timed step's verdict bytes (its stream's buffer; nothing has probed since)
+        dump_outputs(args.dump_outputs,
+                     {"verdict": verdicts[(args.warmup + args.steps - 1) % S].cpu().numpy()})
     # the secondary legs (one stream; cache-resident): the median of 5 timed
     # regions each, so one host hiccup inside a ~1 ms region does not move them
     def med(nstreams, nbatch):
         return float(np.median([timed(nstreams, nbatch) for _ in range(5)]))
-    serial_elapsed = med(1, NB) if S > 1 else elapsed
-    # L3-resident: two batches alternate (window + both batches fit the 256 MiB cache)
-    l3_elapsed = med(S, 2) if NB > 2 else elapsed
-    l3_serial = med(1, 2) if NB > 2 else serial_elapsed
+    serial_elapsed = l3_elapsed = l3_serial = None
+    if args.full:
+        serial_elapsed = med(1, NB) if S > 1 else elapsed
+        # L3-resident: two batches alternate (window + both batches fit the 256 MiB cache)
+        l3_elapsed = med(S, 2) if NB > 2 else elapsed
+        l3_serial = med(1, 2) if NB > 2 else serial_elapsed
     v.set_stream(streams[0].cuda_stream)
 
     # verdicts of batch 0 (for the conflict rate and the CPU parity sample)
@@ -1675,16 +1719,18 @@ def main():
     forced = batches[0]["forced"]
     v0 = np.maximum(v0, forced)
 
-    # per-kernel device time (separate pass over the ring; events on the launch stream)
-    v.enable_timing(True)
-    acc = {}
-    for k in range(args.steps):
-        v.probe_device(structs[k % NB][0])
-        v.synchronize()
-        for key, val in v.timing().items():
-            acc.setdefault(key, []).append(val)
-    v.enable_timing(False)
-    tm = {k: float(np.mean(vals)) for k, vals in acc.items()}
+    tm = None
+    if args.full:
+        # per-kernel device time (separate pass over the ring; events on the launch stream)
+        v.enable_timing(True)
+        acc = {}
+        for k in range(args.steps):
+            v.probe_device(structs[k % NB][0])
+            v.synchronize()
+            for key, val in v.timing().items():
+                acc.setdefault(key, []).append(val)
+        v.enable_timing(False)
+        tm = {k: float(np.mean(vals)) for k, vals in acc.items()}
 
     n_keys = v.keys
     n_r = int(np.mean([b["n"] for b in batches]))
@@ -1703,9 +1749,11 @@ def main():
                         axis=0)
         B = int((keys_g * (lhat + 12)).sum() + (rng_g * (2 * lhat + 16)).sum() + (T + 7) // 8)
     WG = v.tile_key_words if v.layout == hsc.LAYOUT_COMPACT and not args.compact_wide else 0
-    kern = kernel_bytes(v.layout, W if WG else v.code_words, n_keys, n_r, T, tm, WG, False)
+    kern = kernel_bytes(v.layout, W if WG else v.code_words, n_keys, n_r, T, tm, WG, False) if tm else None
     ms_per_step = elapsed / args.steps * 1e3
-    frac = lambda el: B / (el / args.steps) / 1e9 / HBM_PEAK_GBS
+    # (the legs a plain run leaves out, --full, are None in its line)
+    per_step_ms = lambda el: None if el is None else el / args.steps * 1e3
+    frac = lambda el: None if el is None else B / (el / args.steps) / 1e9 / HBM_PEAK_GBS
     checks = T * args.steps
     out = {
         "metric": METRIC,
@@ -1728,7 +1776,7 @@ def main():
             "logged_writes_per_gpu": n_w,
             "parallelism": "one GPU (bench.py --gpus N: the multi-GPU context, bench_multi)",
             "streams": S,
-            "serial_ms_per_step": serial_elapsed / args.steps * 1e3,
+            "serial_ms_per_step": per_step_ms(serial_elapsed),
             "ring_batches": NB,
             "window_layout": {hsc.LAYOUT_NARROW: "narrow (u32 tile-relative keys)",
                               hsc.LAYOUT_COMPACT: (f"compact tiles ({WG}-word keys gid || code, "
@@ -1743,7 +1791,7 @@ def main():
             # the probe phase as SURVEY 8(d) defines it: B over the device time of
             # one batch (the timed loop runs batches back to back over the ring)
             "bound": "hbm",
-            "kernel": "probe phase (" + ", ".join(kern) + ")",
+            "kernel": "probe phase" + (" (" + ", ".join(kern) + ")" if kern else ""),
             "achieved": B / (ms_per_step * 1e-3) / 1e9,
             "peak": HBM_PEAK_GBS,
             "unit": "GB/s",
@@ -1767,17 +1815,17 @@ def main():
             "l3_resident": {
                 "batches": 2,
                 "input_bytes": int(batches[0]["bytes"] + batches[min(1, NB - 1)]["bytes"]),
-                "ms_per_step": l3_elapsed / args.steps * 1e3,
-                "serial_ms_per_step": l3_serial / args.steps * 1e3,
+                "ms_per_step": per_step_ms(l3_elapsed),
+                "serial_ms_per_step": per_step_ms(l3_serial),
                 "frac": frac(l3_elapsed),
                 "frac_1stream": frac(l3_serial),
-                "value": checks / l3_elapsed},
+                "value": checks / l3_elapsed} if args.full else None,
         },
         "probe_phase": {
             "event_total_ms": tm["probe_total_ms"],
             "kernels": kern,
             "join_records": tm["records"], "tiles": tm["tiles"],
-        },
+        } if tm else None,
         "ingest_ms": ingest_ms,
         # window build (sort + dedupe + summaries), SURVEY 8(d): reported apart
         # from the probe phase; bytes = N_w * (L^ + 8 LSN + 4 group)

@@ -4,7 +4,7 @@
 # comdb2_amd/lib/ab), ROUNDS times.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-ARGS=${AB_ARGS:---steps 20 --warmup 3 --no-cpu}
+ARGS=${AB_ARGS:---steps 20 --warmup 3 --full --no-cpu}
 ROUNDS=${ROUNDS:-2}
 AB_DIR=${AB_DIR:-comdb2_amd/lib/ab}
 for r in $(seq 1 $ROUNDS); do

@@ -5,8 +5,9 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 TAG=${TAG:-r01i} PASSES=kt,fetch,write bash scripts/profile.sh || exit $?
-timeout -k 10 400 python bench.py > gpurun_out/re_bench.log 2>&1 || exit $?
-tail -c 300 gpurun_out/re_bench.log
-timeout -k 10 400 python bench.py --config 3 --check --no-cpu > gpurun_out/re_c3.log 2>&1 || exit $?
-timeout -k 10 500 python bench.py --config 5 --check --no-cpu > gpurun_out/re_c5.log 2>&1 || exit $?
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
+timeout -k 10 400 python bench.py --full > "$OUT/re_bench.log" 2>&1 || exit $?
+tail -c 300 "$OUT/re_bench.log"
+timeout -k 10 400 python bench.py --config 3 --full --check --no-cpu > "$OUT/re_c3.log" 2>&1 || exit $?
+timeout -k 10 500 python bench.py --config 5 --full --check --no-cpu > "$OUT/re_c5.log" 2>&1 || exit $?
 echo done

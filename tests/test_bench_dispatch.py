@@ -67,6 +67,16 @@ def test_config4_gpus_must_match_world_size():
     assert "bench.py --gpus 2 under WORLD_SIZE 4" in r.stderr
 
 
+@pytest.mark.parametrize("extra", [["--gpus", "2"], ["--config", "4"], ["--config", "1"]])
+def test_dump_outputs_is_for_one_gpu_check_batches(extra, tmp_path):
+    """--dump-outputs writes the one-GPU check batch's verdicts (configs 2, 3,
+    5); any other run refuses it before touching anything."""
+    r = _run(extra + ["--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "d")])
+    assert r.returncode == 2, r.stderr[-2000:]
+    assert "--dump-outputs: one-GPU runs of configs 2, 3 and 5 only" in r.stderr
+    assert not (tmp_path / "d").exists() and r.stdout == ""
+
+
 def test_multi_line_carries_cpu_baseline_traffic_and_oracle_parity():
     """Static check of bench_multi: the N > 1 line gets the oracle CPU baseline
     on owner 0's read sets (with parity against the merged GPU verdicts) and

@@ -32,7 +32,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 
 namespace hsc {
 
@@ -43,14 +42,8 @@ constexpr uint32_t kCTRows = 1u << kCTLog2;  // rows per tile
 // enough for every CU (4096-probe chunks left 110 of 256 idle; chunks sized
 // to one workgroup per CU -- 2560 probes, 232 workgroups -- measured the same,
 // 32.4 vs 32.9 us (r05): a workgroup's time is not its probes in series)
-#ifndef HSC_CLOC_THREADS
-#define HSC_CLOC_THREADS 512
-#endif
-#ifndef HSC_CLOC_P
-#define HSC_CLOC_P 4
-#endif
-constexpr int kCLocThreads = HSC_CLOC_THREADS;
-constexpr int kCLocP = HSC_CLOC_P;           // probes per locate thread
+constexpr int kCLocThreads = 512;
+constexpr int kCLocP = 4;  // probes per locate thread
 constexpr uint32_t kCChunk = kCLocThreads * kCLocP;
 static_assert(kCChunk <= 4096, "in-chunk ranks are 12 bits");
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
@@ -350,13 +343,10 @@ __global__ __launch_bounds__(kCLocThreads) void k_locate_c(CTiles ct, WinView wt
 // ---- join ----
 // #rows < x (LE: <= x) of the tile: x's word-0 bucket, then a binary search
 // of that bucket's rows (sorted order, full-key compares)
-// WL: key words staged in LDS (kw, stride kCTRows); words WL .. WG - 1 are
-// read from the window itself on a tie (kg: the tile's row 0 of word WL,
-// stride glen)
-template <int WG, bool LE, int WL = WG>
+// (kw: the tile's WG key words staged in LDS, stride kCTRows)
+template <int WG, bool LE>
 __device__ __forceinline__ uint32_t tile_count(const uint64_t *kw, const uint32_t *B, int shift,
-                                               uint32_t tn, const uint64_t (&x)[WG], bool &found,
-                                               const uint64_t *kg = nullptr, size_t glen = 0)
+                                               uint32_t tn, const uint64_t (&x)[WG], bool &found)
 {
     constexpr uint32_t T = kCTRows;
     const uint64_t f0 = kw[0];
@@ -373,7 +363,7 @@ __device__ __forceinline__ uint32_t tile_count(const uint64_t *kw, const uint32_
 #pragma unroll
         for (int w = 1; w < WG; ++w)
             if (eq) {
-                v = w < WL ? kw[(size_t)w * T + mid] : kg[(size_t)(w - WL) * glen + mid];
+                v = kw[(size_t)w * T + mid];
                 below = v < x[w];
                 eq = v == x[w];
             }
@@ -399,18 +389,17 @@ __device__ __forceinline__ bool row_eq(const uint64_t *kw, uint32_t r, const uin
 // CU hold 32 waves (the CU's limit).  (r05: staging key words 0-1 only, word 2
 // read from the window on a tie -- 16 KiB less, room for another stream's
 // locate beside two join workgroups -- measured 82.4 vs 78.0 us per batch on
-// two streams, the join 42.7 vs 39.0 us)
+// two streams, the join 42.7 vs 39.0 us: removed, last present in 86048b5)
 constexpr int kCJT = 1024;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // the searches of one record after its tile is staged
-template <int WG, int WL = WG>
+template <int WG>
 __device__ __forceinline__ void join_search(const ProbeWork &work, const CTiles &ct, uint8_t *flags,
                                             const uint64_t *kw, const uint32_t *rank,
                                             const uint32_t *b16, const uint32_t *b128,
                                             const uint32_t *B, uint32_t kind, const u64x2 (&pl)[2],
-                                            const u64x2 ph0, const uint64_t ph1,
-                                            const uint64_t *kg = nullptr)
+                                            const u64x2 ph0, const uint64_t ph1)
 {
     const uint32_t tn = B[kTB] & 0xFFFF;
     const int shift = (int)(B[kTB] >> 16);
@@ -428,11 +417,11 @@ __device__ __forceinline__ void join_search(const ProbeWork &work, const CTiles 
     // a point: #rows <= lo = #rows < lo + (a row equals lo), and a lower-bound
     // search compares the equal row if there is one
     bool eqa = false, eqb = false;
-    if (kind != kCTail) pa = tile_count<WG, false, WL>(kw, B, shift, tn, lo, eqa, kg, ct.len);
+    if (kind != kCTail) pa = tile_count<WG, false>(kw, B, shift, tn, lo, eqa);
     if (kind == kCPoint)
         pb = pa + eqa;
     else if (kind != kCHead)
-        pb = tile_count<WG, true, WL>(kw, B, shift, tn, hi, eqb, kg, ct.len);
+        pb = tile_count<WG, true>(kw, B, shift, tn, hi, eqb);
 #ifdef HSC_STAMPS
     if (threadIdx.x == 0 && work.stamps && pa + pb == 0x7FFFFFFF) flags[0] = 1;
 #endif
@@ -454,7 +443,7 @@ __device__ __forceinline__ void join_search(const ProbeWork &work, const CTiles 
 // column) is the last one <= j.  The column is loaded first, staged, each
 // thread finds its record's chunk by a 9-step LDS search and loads the whole
 // 64-byte record (no bucket entry, no gather) while the rows are in flight.
-template <int WG, bool kTile, int WL = WG>
+template <int WG, bool kTile>
 __device__ __forceinline__ void join_item_s(const ProbeWork &work, const CTiles &ct, uint8_t *flags,
                                             uint32_t xi, uint64_t *kw, uint32_t *rank,
                                             uint32_t *b16, uint32_t *b128, uint32_t *B,
@@ -474,9 +463,9 @@ __device__ __forceinline__ void join_item_s(const ProbeWork &work, const CTiles 
     uint32_t e = 0, cs = 0;
     if (tid < G) e = work.hist[col + tid], cs = work.cst[col + tid];
     const size_t row = ((size_t)tile << kCTLog2) + 2 * tid;
-    u64x2 kv[WL];
+    u64x2 kv[WG];
 #pragma unroll
-    for (int w = 0; w < WL; ++w) kv[w] = *(const u64x2 *)(ct.key + (size_t)w * ct.len + row);
+    for (int w = 0; w < WG; ++w) kv[w] = *(const u64x2 *)(ct.key + (size_t)w * ct.len + row);
     const u32x2 rr = *(const u32x2 *)(ct.rank + row);
     u32x2 bt = {0, 0};
     if (tid < kTBS / 2) bt = *(const u32x2 *)(ct.tb + (size_t)tile * kTBS + 2 * tid);
@@ -498,7 +487,7 @@ __device__ __forceinline__ void join_item_s(const ProbeWork &work, const CTiles 
         A0 = r[0], A1 = r[1], B0 = r[2], B1 = r[3];
     }
 #pragma unroll
-    for (int w = 0; w < WL; ++w) *(u64x2 *)(kw + (size_t)w * T + 2 * tid) = kv[w];
+    for (int w = 0; w < WG; ++w) *(u64x2 *)(kw + (size_t)w * T + 2 * tid) = kv[w];
     *(u32x2 *)(rank + 2 * tid) = rr;
     if (tid < kTBS / 2) *(u32x2 *)(B + 2 * tid) = bt;
     uint32_t m = max(rr.x, rr.y);
@@ -515,31 +504,20 @@ __device__ __forceinline__ void join_item_s(const ProbeWork &work, const CTiles 
     u64x2 pl[2] = {A0, u64x2{A1.x, rt}}, ph0 = B0;
     uint64_t ph1 = B1.x;
     if (kind == kCTail) ph0 = A0, ph1 = A1.x;  // a tail record carries hi in its first half
-    // words past WL: read from the window on a tie (the tile's row 0 of word WL)
-    const uint64_t *kg = WL < WG ? ct.key + (size_t)WL * ct.len + ((size_t)tile << kCTLog2) : nullptr;
-    join_search<WG, WL>(work, ct, flags, kw, rank, b16, b128, B, kind, pl, ph0, ph1, kg);
+    join_search<WG>(work, ct, flags, kw, rank, b16, b128, B, kind, pl, ph0, ph1);
 }
 
-// XCD-contiguous tiles (as the narrow join): measured neutral on config 3
-// (1.100 vs 1.108 G checks/s, r02c), so off by default
-#ifndef HSC_CJOIN_XCD
-#define HSC_CJOIN_XCD 0
-#endif
-constexpr bool kCJoinXcd = HSC_CJOIN_XCD != 0;
-__host__ __device__ inline uint32_t ct_tile_blocks(uint32_t ntiles)
-{
-    return kCJoinXcd ? 8 * ((ntiles + 7) / 8) : ntiles;
-}
-
-template <int WG, int WL = WG>
+// (XCD-contiguous tiles, as the narrow join's: measured neutral on config 3,
+// 1.100 vs 1.108 G checks/s, r02c -- removed, last present in 86048b5)
+template <int WG>
 __global__ __launch_bounds__(kCJT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_join_c(ProbeWork work, CTiles ct, uint8_t *flags)
 {
     constexpr uint32_t T = kCTRows;
     static_assert(T == 2 * kCJT, "a row pair per thread");
     static_assert(kJoinChunk == kCJT && kTileCap == kCJT, "a record per thread");
     extern __shared__ __attribute__((aligned(16))) uint64_t jl[];
-    uint64_t *kw = jl;                                   // [WL][T], sorted
-    uint32_t *rank = (uint32_t *)(jl + (size_t)WL * T);  // [T], sorted order
+    uint64_t *kw = jl;                                   // [WG][T], sorted
+    uint32_t *rank = (uint32_t *)(jl + (size_t)WG * T);  // [T], sorted order
     uint32_t *b16 = rank + T;                            // [T / 16]
     uint32_t *b128 = b16 + T / 16;                       // [T / 128]
     uint32_t *B = b128 + T / 128;                        // [kTBS] the tile's bucket table
@@ -547,18 +525,15 @@ __global__ __launch_bounds__(kCJT) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     uint16_t *Cs = (uint16_t *)(Es + kMaxChunks);         // (run starts < 2 * kCChunk)
     // the first xb blocks take the hot tiles' overflow items in turn (dispatched
     // first: they are the fullest), then one block per tile
-    const uint32_t xb = gridDim.x - ct_tile_blocks(ct.ntiles);
+    const uint32_t xb = gridDim.x - ct.ntiles;
     if (blockIdx.x >= xb) {
-        // neighbouring tiles on one XCD (they share lines of the chunk areas)
-        const uint32_t b = blockIdx.x - xb, tb = gridDim.x - xb;
-        const uint32_t tile = kCJoinXcd ? xcd_chunk(b, tb / 8) : b;
-        if (tile < ct.ntiles) join_item_s<WG, true, WL>(work, ct, flags, tile, kw, rank, b16, b128, B, Es, Cs);
+        join_item_s<WG, true>(work, ct, flags, blockIdx.x - xb, kw, rank, b16, b128, B, Es, Cs);
         return;
     }
     const uint32_t nextra = work.item_off[1];
     for (uint32_t xi = blockIdx.x; xi < nextra; xi += xb) {
         __syncthreads();  // the previous item's LDS reads are done
-        join_item_s<WG, false, WL>(work, ct, flags, xi, kw, rank, b16, b128, B, Es, Cs);
+        join_item_s<WG, false>(work, ct, flags, xi, kw, rank, b16, b128, B, Es, Cs);
     }
 }
 
@@ -611,24 +586,15 @@ hipError_t launch_join_c(const CTiles &ct, const ProbeWork &work, uint32_t max_i
 {
     if (max_items == 0 || ct.n == 0 || ct.ntiles == 0) return hipSuccess;
     const uint32_t extra = max_items - ct.ntiles;
-    const uint32_t blocks = ct_tile_blocks(ct.ntiles) + (extra < 512 ? extra : 512);
-    // key words staged per tile (HSC_CJOIN_WL, A/B; default all): the rest
-    // are read from the window on a tie
-    static const int wl_env = getenv("HSC_CJOIN_WL") ? atoi(getenv("HSC_CJOIN_WL")) : 0;
-    const int WL = wl_env >= 1 && wl_env < ct.WG ? wl_env : ct.WG;
-    const size_t lds = 8 * (size_t)WL * kCTRows + 4 * (size_t)kCTRows + 4 * (kCTRows / 16) +
+    const uint32_t blocks = ct.ntiles + (extra < 512 ? extra : 512);
+    const size_t lds = 8 * (size_t)ct.WG * kCTRows + 4 * (size_t)kCTRows + 4 * (kCTRows / 16) +
                        4 * (kCTRows / 128) + 4 * kTBS + 6 * (size_t)kMaxChunks;
-#define HSC_JOIN_C(WG_, WL_) k_join_c<WG_, WL_><<<blocks, kCJT, lds, s>>>(work, ct, flags)
-    switch (ct.WG * 4 + WL) {
-    case 1 * 4 + 1: HSC_JOIN_C(1, 1); break;
-    case 2 * 4 + 1: HSC_JOIN_C(2, 1); break;
-    case 2 * 4 + 2: HSC_JOIN_C(2, 2); break;
-    case 3 * 4 + 1: HSC_JOIN_C(3, 1); break;
-    case 3 * 4 + 2: HSC_JOIN_C(3, 2); break;
-    case 3 * 4 + 3: HSC_JOIN_C(3, 3); break;
+    switch (ct.WG) {
+    case 1: k_join_c<1><<<blocks, kCJT, lds, s>>>(work, ct, flags); break;
+    case 2: k_join_c<2><<<blocks, kCJT, lds, s>>>(work, ct, flags); break;
+    case 3: k_join_c<3><<<blocks, kCJT, lds, s>>>(work, ct, flags); break;
     default: return hipErrorInvalidValue;
     }
-#undef HSC_JOIN_C
     return hipGetLastError();
 }
 

@@ -25,7 +25,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
 #include <utility>
 #include <vector>
@@ -65,9 +64,6 @@ __device__ __forceinline__ uint32_t gw_bits(size_t nops, const uint8_t *is_write
     return w;
 }
 
-// (bad != null: the observed ids' range check here too -- bit 0 -- for the
-// builds whose edge pass does not check them itself; the txns' range and order
-// are k_gw_place's)
 // out[0] / out[1] = the varying bits of the writers' key / txn, out[2] = 0
 // (their gid): OR & ~AND over k_gw_place's block partials; out[3] / out[4]
 // the ANDs
@@ -100,25 +96,12 @@ __global__ __launch_bounds__(1024) void k_vary_reduce(uint32_t nb, const uint64_
     }
 }
 
-__global__ __launch_bounds__(kGwThreads) void k_gw_count(size_t nops, const uint8_t *is_write, uint32_t *bc,
-                                                         const uint32_t *observed, uint32_t ntxn, uint32_t *bad)
+__global__ __launch_bounds__(kGwThreads) void k_gw_count(size_t nops, const uint8_t *is_write, uint32_t *bc)
 {
     __shared__ uint32_t wsum[kGwThreads / 64];
     uint32_t cnt;
     const size_t base = (size_t)blockIdx.x * (kGwThreads * kGwItems);
     (void)gw_bits(nops, is_write, base, cnt);
-    if (bad) {  // (coalesced: op base + 256 k + t)
-        uint32_t b = 0;
-#pragma unroll
-        for (int k = 0; k < kGwItems; ++k) {
-            const size_t i = base + (size_t)k * kGwThreads + threadIdx.x;
-            if (i >= nops) break;
-            const uint32_t o = observed[i];
-            b |= (o != kNone && o >= ntxn) ? 1u : 0u;
-        }
-        const uint64_t any = __ballot(b != 0);
-        if (any && b) atomicOr(bad, b);
-    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
@@ -520,26 +503,26 @@ __global__ void k_edges_reads_pk(size_t nops, const uint32_t *txn, const uint64_
 // bucket) searches pk as before.  (A first form with 14 full 8-byte entries
 // per 128-byte line, 512 MB: the search 3.5 -> 2.85 ms, but stored a u64 per
 // thread 128 bytes apart -- 5 GB of partial-line writes, 1.05 ms.)
-// LW = 8: 64-byte lines, 12 offsets, about 8 writers per bucket (default);
-// LW = 16: 128-byte lines, 28 offsets, about 16 writers per bucket -- the same
-// table bytes, ~0.3 % of the buckets overflow instead of ~5 %, but measured
-// slower (r06x).
+// kPtLine = 8 words: 64-byte lines, 12 offsets, about 8 writers per bucket.
+// (128-byte lines with 28 offsets and about 16 writers per bucket -- the same
+// table bytes, ~0.3 % of the buckets overflow instead of ~5 % -- measured
+// slower, r06x.)
+constexpr int kPtLine = 8;
 __device__ __forceinline__ uint64_t bucket_start(const PairPack &pp, uint64_t b)
 {
     return pp.base + (pp.shift >= 64 ? 0 : b << pp.shift);
 }
 
-// LW threads per bucket, one 8-byte word each: coalesced lines.  (The bucket
+// kPtLine threads per bucket, one 8-byte word each: coalesced lines.  (The bucket
 // bounds searched here instead of by k_pair_dir -- lane 0 of each bucket,
 // shuffled to the rest -- measured 1.07 ms against 0.28 ms for the two
 // passes, r06aa: 8 searches per wave instead of 64.)
-template <int LW>
 __global__ void k_pair_table(uint32_t nu, const uint64_t *pk, const uint32_t *dir, uint64_t nb, PairPack pp,
                              uint64_t *tab)
 {
     const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t b = id / LW;
-    const int w = (int)(id % LW);
+    const uint64_t b = id / kPtLine;
+    const int w = (int)(id % kPtLine);
     if (b >= nb) return;
     const uint32_t lo = dir[b], hi = dir[b + 1];
     const uint32_t n = hi - lo;
@@ -555,14 +538,13 @@ __global__ void k_pair_table(uint32_t nu, const uint64_t *pk, const uint32_t *di
         const uint32_t e1 = j1 < n ? (uint32_t)(pk[lo + j1] - s0) : 0xFFFFFFFFu;
         v = (uint64_t)e0 | ((uint64_t)e1 << 32);
     }
-    tab[(uint64_t)LW * b + w] = v;
+    tab[(uint64_t)kPtLine * b + w] = v;
 }
 
-// NT: the op columns (read once) and the rows (not read back by this step's
+// The op columns (read once) and the rows (not read back by this step's
 // cover or cut on the usual path) move with non-temporal loads / stores, so
 // they do not push the bucket lines -- the only re-read data -- out of the
 // caches
-template <int LW, bool NT>
 __global__ void k_edges_reads_pt(size_t nops, const uint32_t *txn, const uint64_t *key,
                                  const uint8_t *is_write, const uint32_t *observed, uint32_t nu,
                                  const uint64_t *wkey, const uint64_t *wtxn, const uint64_t *pk,
@@ -573,12 +555,12 @@ __global__ void k_edges_reads_pt(size_t nops, const uint32_t *txn, const uint64_
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nops) return;
     uint64_t wr = ~0ull, rw = ~0ull;
-    const uint32_t ob0 = NT ? __builtin_nontemporal_load(observed + i) : observed[i];
-    const bool isw = (NT ? __builtin_nontemporal_load(is_write + i) : is_write[i]) != 0;
+    const uint32_t ob0 = __builtin_nontemporal_load(observed + i);
+    const bool isw = __builtin_nontemporal_load(is_write + i) != 0;
     // (every op's observed id checked, a write's too: the build's contract)
     if (!obs_bad(ob0, chk_n, bad) && !isw) {
-        const uint32_t r = NT ? __builtin_nontemporal_load(txn + i) : txn[i], ob = ob0;
-        const uint64_t k = NT ? __builtin_nontemporal_load(key + i) : key[i];
+        const uint32_t r = __builtin_nontemporal_load(txn + i), ob = ob0;
+        const uint64_t k = __builtin_nontemporal_load(key + i);
         if (ob != kNone && ob != r) wr = ((uint64_t)ob << 32) | r;
         if (!skip_rw && (k & ~pp.km) == pp.kc) {
             uint64_t km[6], tm[6];
@@ -589,11 +571,11 @@ __global__ void k_edges_reads_pt(size_t nops, const uint32_t *txn, const uint64_
                 const uint64_t x = pair_key(pp, kp) | (ob == kNone ? 0 : bits_compress(ob, pp.tm, tm));
                 const bool strict = ob != kNone;
                 const uint64_t b = pair_bucket(pp, x);
-                constexpr int kPtE = 2 * (LW - 2);
-                const u64x2 *line = (const u64x2 *)(tab + (uint64_t)LW * b);
-                u64x2 e[LW / 2];
+                constexpr int kPtE = 2 * (kPtLine - 2);
+                const u64x2 *line = (const u64x2 *)(tab + (uint64_t)kPtLine * b);
+                u64x2 e[kPtLine / 2];
 #pragma unroll
-                for (int q = 0; q < LW / 2; ++q) e[q] = line[q];
+                for (int q = 0; q < kPtLine / 2; ++q) e[q] = line[q];
                 const uint64_t hd = e[0].x;
                 const uint32_t n = (uint32_t)(hd & 0x7FFFFFFFu), lo = (uint32_t)(hd >> 32);
                 bool have = false;
@@ -640,13 +622,8 @@ __global__ void k_edges_reads_pt(size_t nops, const uint32_t *txn, const uint64_
         }
     }
     const size_t s = (size_t)nu + 2 * i;
-    if (NT) {
-        __builtin_nontemporal_store(wr, ew + s);
-        __builtin_nontemporal_store(rw, ew + s + 1);
-    } else {
-        ew[s] = wr;
-        ew[s + 1] = rw;
-    }
+    __builtin_nontemporal_store(wr, ew + s);
+    __builtin_nontemporal_store(rw, ew + s + 1);
     back_push(diff, wr);
     back_push(diff, rw);
     if (et) {
@@ -654,185 +631,6 @@ __global__ void k_edges_reads_pt(size_t nops, const uint32_t *txn, const uint64_
         eg[s] = 0;
         et[s + 1] = kDepRW;
         eg[s + 1] = 0;
-    }
-}
-
-// ---- partitioned read search (the packed writers) ----
-// k_edges_reads_pk answers each read with a directory line and a search of
-// pk: two dependent random lines per read over a 33M-writer array (config 4:
-// 3.4 ms of a 10.5 ms step).  Instead the reads are partitioned by directory
-// range (2^14 partitions of ~2k writers): one pass counts, one scatters the
-// search items (x, reader) into their partitions, and a workgroup per
-// partition stages its writers in LDS once and answers every item there --
-// the reads' random accesses become streams plus LDS searches.  Edge rows:
-// [nu, nu + nops) the wr edge of op i, [nu + nops, + items + fallbacks) the
-// rw edges in partition order (raw rows carry no slot meaning; a full build
-// sorts them).
-constexpr int kRpBitsMax = 14;        // at most 2^14 partitions
-constexpr uint32_t kRpLds = 6144;     // writers a partition stages (48 KiB of LDS)
-constexpr int kRpThreads = 256;
-
-struct RpArgs {
-    size_t nops;
-    const uint32_t *txn;
-    const uint64_t *key;
-    const uint8_t *is_write;
-    const uint32_t *observed;
-    uint32_t nu;
-    const uint64_t *wkey, *wtxn, *pk;
-    const uint32_t *dir;
-    uint32_t ps;         // partition = bucket >> ps
-    uint32_t np;         // partitions (incl. the one past the range)
-    uint32_t *cnt;       // [np + 1] counts, then offsets (exclusive scan; [np] = items)
-    uint32_t *cur;       // [np + 1] cursors; cur[np] = fallback rows
-    ulonglong2 *items;   // (x, reader | strict << 32)
-    uint64_t *ew;        // edge rows
-    uint64_t *et;        // types (full builds) or null
-    uint32_t *eg;
-    uint32_t *diff;      // raw builds: the cover's interval diffs of backward edges (else null)
-    int skip_rw;
-};
-
-// x of a read's "first writer after (k, ob)" search, or false when it needs
-// none (key without writers) / the row search (an observed txn outside the
-// writers' bits).  *fb: the row search is needed.
-__device__ __forceinline__ bool rp_x(const PairPack &pp, uint64_t k, uint32_t ob, uint64_t *x, bool *fb)
-{
-    *fb = false;
-    if ((k & ~pp.km) != pp.kc) return false;
-    if (ob != kNone && (ob & ~pp.tm) != pp.tc) {
-        *fb = true;
-        return false;
-    }
-    uint64_t km[6], tm[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) km[q] = pp.kmv[q], tm[q] = pp.tmv[q];
-    *x = pair_key(pp, bits_compress(k, pp.km, km)) | (ob == kNone ? 0 : bits_compress(ob, pp.tm, tm));
-    return true;
-}
-
-__global__ __launch_bounds__(kRpThreads) void k_rp_count(RpArgs a, PairPack pp)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.nops || a.skip_rw || a.is_write[i]) return;
-    uint64_t x;
-    bool fb;
-    if (rp_x(pp, a.key[i], a.observed[i], &x, &fb))
-        atomicAdd(&a.cnt[(uint32_t)(pair_bucket(pp, x) >> a.ps)], 1u);
-}
-
-// exclusive scan of cnt[0, np) in place, cnt[np] = total; cur zeroed
-__global__ __launch_bounds__(1024) void k_rp_scan(RpArgs a)
-{
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, per = (a.np + 1023) / 1024;
-    const uint32_t b = t * per, e = min(a.np, b + per);
-    uint32_t s = 0;
-    for (uint32_t i = b; i < e; ++i) s += a.cnt[i];
-    part[t] = s;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {  // inclusive scan of the parts
-        const uint32_t v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - s;
-    for (uint32_t i = b; i < e; ++i) {
-        const uint32_t c = a.cnt[i];
-        a.cnt[i] = run;
-        run += c;
-    }
-    if (t == 1023) a.cnt[a.np] = part[1023];
-    for (uint32_t i = t; i <= a.np; i += 1024) a.cur[i] = 0;
-}
-
-__global__ __launch_bounds__(kRpThreads) void k_rp_scatter(RpArgs a, PairPack pp)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.nops) return;
-    uint64_t wr = ~0ull;
-    if (!a.is_write[i]) {
-        const uint32_t r = a.txn[i], ob = a.observed[i];
-        const uint64_t k = a.key[i];
-        if (ob != kNone && ob != r) wr = ((uint64_t)ob << 32) | r;
-        uint64_t x;
-        bool fb;
-        if (!a.skip_rw && rp_x(pp, k, ob, &x, &fb)) {
-            const uint32_t p = (uint32_t)(pair_bucket(pp, x) >> a.ps);
-            const uint32_t slot = a.cnt[p] + atomicAdd(&a.cur[p], 1u);
-            a.items[slot] = make_ulonglong2(x, (uint64_t)r | (ob != kNone ? 1ull << 32 : 0));
-        } else if (!a.skip_rw && fb) {  // the row search (rare): its rw row after the items
-            uint32_t lo = 0, hi = a.nu;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                const uint64_t mk = a.wkey[mid], mt = a.wtxn[mid];
-                if (mk < k || (mk == k && mt <= ob))
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            if (lo < a.nu && a.wkey[lo] == k && a.wtxn[lo] != r) {
-                const size_t o = (size_t)a.nu + a.nops + a.cnt[a.np] + atomicAdd(&a.cur[a.np], 1u);
-                const uint64_t row = ((uint64_t)r << 32) | a.wtxn[lo];
-                a.ew[o] = row;
-                if (a.et) a.et[o] = kDepRW, a.eg[o] = 0;
-                back_row(a.diff, row);
-            }
-        }
-    }
-    const size_t s = (size_t)a.nu + i;
-    a.ew[s] = wr;
-    if (a.et) a.et[s] = kDepWR, a.eg[s] = 0;
-    back_row(a.diff, wr);
-}
-
-__global__ __launch_bounds__(kRpThreads) void k_rp_join(RpArgs a, PairPack pp)
-{
-    __shared__ uint64_t sw[kRpLds];
-    const uint32_t p = blockIdx.x;
-    const uint32_t i0 = a.cnt[p], i1 = p + 1 < a.np ? a.cnt[p + 1] : a.cnt[a.np];
-    if (i0 == i1) return;
-    const uint64_t nb = (1ull << pp.D) + 1;  // dir entries [0, 2^D + 1]
-    const uint32_t w0 = a.dir[min((uint64_t)p << a.ps, nb)];
-    const uint32_t w1 = a.dir[min(((uint64_t)p + 1) << a.ps, nb)];
-    const uint32_t n = w1 - w0;
-    const bool lds = n <= kRpLds;
-    if (lds)
-        for (uint32_t j = threadIdx.x; j < n; j += kRpThreads) sw[j] = a.pk[w0 + j];
-    __syncthreads();
-    uint64_t tm[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) tm[q] = pp.tmv[q];
-    const uint64_t tmask = pp.tb >= 64 ? ~0ull : (1ull << pp.tb) - 1;
-    for (uint32_t it = i0 + threadIdx.x; it < i1; it += kRpThreads) {
-        const ulonglong2 q = a.items[it];
-        const uint64_t x = q.x;
-        const uint32_t r = (uint32_t)q.y;
-        const bool strict = (q.y >> 32) & 1;
-        uint32_t lo = 0, hi = n;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            const uint64_t v = lds ? sw[mid] : a.pk[w0 + mid];
-            if (strict ? v <= x : v < x)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        uint64_t rw = ~0ull;
-        const uint32_t g = w0 + lo;
-        if (g < a.nu) {
-            const uint64_t v = lo < n && lds ? sw[lo] : a.pk[g];
-            const uint64_t kp = pp.tb >= 64 ? 0 : x >> pp.tb;
-            if ((pp.tb >= 64 ? 0 : v >> pp.tb) == kp) {
-                const uint32_t wt = (uint32_t)(bits_expand(v & tmask, pp.tm, tm) | pp.tc);
-                if (wt != r) rw = ((uint64_t)r << 32) | wt;
-            }
-        }
-        const size_t o = (size_t)a.nu + a.nops + it;
-        a.ew[o] = rw;
-        if (a.et) a.et[o] = kDepRW, a.eg[o] = 0;
-        back_row(a.diff, rw);
     }
 }
 
@@ -1072,18 +870,12 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     CK(g.ww2.ensure(16 * wcap));
     CK(g.wl2.ensure(8 * wcap));
     const size_t gwb = (nops + kGwThreads * kGwItems - 1) / (kGwThreads * kGwItems);
-    // the partitioned read search (A/B, HSC_GRAPH_RP=1) does not check the
-    // observed ids: the count pass does then (else the edge pass, guarded)
-    static const bool rp_env = getenv("HSC_GRAPH_RP") != nullptr && atoi(getenv("HSC_GRAPH_RP")) != 0;
-    const bool obs_in_count = rp_env;
     CK(g.flags.ensure(4 * (gwb + 2)));
     CK(g.gvary.ensure(32 * (gwb + 3)));
     CK(g.scratch.ensure(std::max(scan_scratch_bytes(gwb + 1), (size_t)1024)));
     uint32_t *bc = g.flags.as<uint32_t>();
     CK(hipMemsetAsync(bc + gwb, 0, 8, s));  // the total slot and the check's bits
-    if (gwb)
-        k_gw_count<<<(unsigned)gwb, kGwThreads, 0, s>>>(nops, in.is_write, bc, in.observed, in.ntxn,
-                                                         in.check && obs_in_count ? bc + gwb + 1 : nullptr);
+    if (gwb) k_gw_count<<<(unsigned)gwb, kGwThreads, 0, s>>>(nops, in.is_write, bc);
     CK(scan_exclusive_u32(bc, gwb + 1, g.scratch.as<uint32_t>(), s));
     if (gwb)
         k_gw_place<<<(unsigned)gwb, kGwThreads, 0, s>>>(nops, in.txn, in.key, in.is_write, bc, g.wg.as<uint32_t>(),
@@ -1119,8 +911,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
         // writers gathered in op order from txn-ordered ops are ordered by
         // txn already: the stable passes need only the key bits (config 4:
         // 3 passes instead of 6)
-        static const bool no_skip = getenv("HSC_GRAPH_NO_TXN_SKIP") != nullptr;  // (A/B)
-        if (packed && txn_sorted && !no_skip && P.nl > 0 && P.limb[P.nl - 1] == 1) P.skip = P.bits[P.nl - 1];
+        if (packed && txn_sorted && P.nl > 0 && P.limb[P.nl - 1] == 1) P.skip = P.bits[P.nl - 1];
     }
     // the packed writers' layout (PairPack's key / txn bits) is known from the
     // place pass's masks: a raw build's ww rows come out of the sort's unpack
@@ -1133,8 +924,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
         compress_moves(pp.tm, pp.tmv);
         pp.tb = __builtin_popcountll(pp.tm);
     }
-    static const bool no_ww_fuse = getenv("HSC_GRAPH_NO_WW_FUSE") != nullptr;  // (A/B)
-    const bool ww_fused = packed && nops && !full && !in.n_extra && !rp_env && !no_ww_fuse;
+    const bool ww_fused = packed && nops && !full && !in.n_extra;
     if (ww_fused) {
         const size_t ecap0 = std::max<size_t>(64, ((size_t)nw + 2 * nops + 63) & ~(size_t)63);
         CK(g.ew.ensure(8 * ecap0));
@@ -1142,13 +932,11 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     DBuf *dw = &g.ww2;
     uint64_t *lsn_d = nullptr;  // packed: the distinct packed keys themselves (no LSN input, I = 0)
     // the packed build reads its writers as the packed keys alone (the ww
-    // rows, the searches and their fallbacks): the distinct rows are written
-    // for the partitioned search's A/B only
-    const bool writer_rows = !packed || rp_env;
+    // rows, the searches and their fallbacks): no distinct rows are written
     if (packed) {
         CK(packed_sort_dedupe(P, nw, g.wg.as<uint32_t>(), g.ww.as<uint64_t>(), nullptr, wcap,
                               g.wl.as<uint64_t>(), g.wl2.as<uint64_t>(), nullptr, nullptr, nullptr, 0,
-                              writer_rows ? g.wg2.as<uint32_t>() : nullptr, g.ww2.as<uint64_t>(), wcap, &lsn_d,
+                              nullptr, g.ww2.as<uint64_t>(), wcap, &lsn_d,
                               g.count.as<uint32_t>(), g.scratch.p, g.scratch.bytes, s,
                               g.count.as<uint32_t>() + 28,  // (its stall flag: read after the build)
                               ww_fused ? g.ew.as<uint64_t>() : nullptr, ww_fused ? &pp : nullptr));
@@ -1174,7 +962,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     uint64_t meta[5] = {0, 0, 0, 0, 0};
     // (the edge pass's check word, g.count's u32 30, cleared by the same kernel)
     uint32_t *ebad = g.count.as<uint32_t>() + 30;
-    const uint32_t chk_n = in.check && !obs_in_count ? std::max<uint32_t>(in.ntxn, 1) : 0;
+    const uint32_t chk_n = in.check ? std::max<uint32_t>(in.ntxn, 1) : 0;
     g.edge_bad = chk_n ? ebad : nullptr;
     g.post = g.count.as<uint32_t>() + 29;  // [-1] the writer sort's stall flag, [0] backward rows
                                            // listed, [1] the edge check's bits
@@ -1186,8 +974,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     // 2. edges (capacity for the widest layout: nu + 2 nops + extras)
     const size_t ne_cap = (size_t)nu + 2 * nops + in.n_extra;
     const size_t ecap = std::max<size_t>(64, (ne_cap + 63) & ~(size_t)63);
-    size_t rw_rows = 0;
-    bool slot_layout = false, diff_done = false, back_listed = false;
+    bool back_listed = false;
     CK(g.ew.ensure(8 * ecap));
     CK(g.et.ensure(8 * ecap));
     CK(g.eg.ensure(4 * ecap));
@@ -1198,23 +985,15 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     uint32_t *eg = full || in.n_extra ? g.eg.as<uint32_t>() : nullptr;
     if (nu && !(packed && nops)) k_edges_ww<<<blocks(nu), 256, 0, s>>>(nu, wkey, wtxn, g.ew.as<uint64_t>(), et, eg);
     if (nops && packed && nu) {
-        // about kPer writers per bucket, at most 2^kDMax buckets (diagnostics:
-        // HSC_GRAPH_DIR = "per,dmax").  Config 4 (33M writers, r05o): 32 / 2^20
-        // 11.2 ms per step, 8 / 2^23 10.4 ms (a read's search touches the
-        // directory line and one line of pk instead of ~3), 4 / 2^24 10.4,
-        // 2 / 2^25 10.6 (the directory's own build grows)
-        // bucket lines of kLine words (HSC_GRAPH_PT_LINE = 8 | 16, an A/B):
-        // twice the writers per bucket with the 128-byte lines -- slower
-        // (r06x, config 4: the search 2.28 -> 2.62 ms; a random 64-byte line
-        // costs less than a 128-byte one, the overflow searches saved less)
-        static int kPer = 8, kDMax = 23, kLine = 8;
-        static const bool env_read = [] {
-            if (const char *v = getenv("HSC_GRAPH_PT_LINE")) kLine = atoi(v) == 16 ? 16 : 8;
-            if (kLine == 16) kPer = 16, kDMax = 22;
-            if (const char *v = getenv("HSC_GRAPH_DIR")) sscanf(v, "%d,%d", &kPer, &kDMax);
-            return true;
-        }();
-        (void)env_read;
+        // about kPer writers per bucket, at most 2^kDMax buckets.  Config 4
+        // (33M writers, r05o): 32 / 2^20 11.2 ms per step, 8 / 2^23 10.4 ms (a
+        // read's search touches the directory line and one line of pk instead
+        // of ~3), 4 / 2^24 10.4, 2 / 2^25 10.6 (the directory's own build
+        // grows).  (Bucket lines of 16 words, twice the writers per bucket:
+        // slower -- r06x, config 4: the search 2.28 -> 2.62 ms; a random
+        // 64-byte line costs less than a 128-byte one, the overflow searches
+        // saved less.)
+        constexpr int kPer = 8, kDMax = 23;
         pp.D = 1;
         while (pp.D < kDMax && ((size_t)kPer << pp.D) < nu) ++pp.D;
         CK(g.pdir.ensure(4 * (((size_t)1 << pp.D) + 2)));
@@ -1228,80 +1007,35 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
         pp.shift = 0;  // (last - base) >> shift < 2^D
         while (pp.shift < 64 && ((pp.last - pp.base) >> pp.shift) >= ((uint64_t)1 << pp.D)) ++pp.shift;
         k_pair_dir<<<blocks(((size_t)1 << pp.D) + 2), 256, 0, s>>>(nu, pkv, pp, g.pdir.as<uint32_t>());
-        // the partitioned read search: measured slower on config 4 (r06c trace:
-        // count 3.0 + scatter 3.2 + join 1.0 ms against 3.5 ms for the
-        // directory search -- the count's per-read global atomics on 16k
-        // partition counters), so off unless HSC_GRAPH_RP=1 (A/B)
-        const bool rp = rp_env;
-        // bucket lines (HSC_GRAPH_PT=0: the directory + pk search, an A/B)
-        static const bool pt = getenv("HSC_GRAPH_PT") == nullptr || atoi(getenv("HSC_GRAPH_PT")) != 0;
-        // raw builds (the sharded SCC's): the cover's backward-edge diffs as
-        // the rows are emitted (ww rows are forward: txns ascend inside a key)
-        uint32_t *diff = nullptr;
+        // (a partitioned read search -- the reads scattered into 2^14 directory
+        // ranges, a workgroup per range staging its writers in LDS -- measured
+        // slower on config 4, r06c trace: count 3.0 + scatter 3.2 + join 1.0 ms
+        // against 3.5 ms for the directory search, the count's per-read global
+        // atomics on 16k partition counters; removed, last present in 86048b5)
+        // raw builds (the sharded SCC's): the backward rows themselves listed
+        // as the rows are emitted (ww rows are forward: txns ascend inside a
+        // key; the counter: g.count's u32 29, cleared by k_graph_meta)
         BackSink sink{nullptr, nullptr, nullptr, 0};
         if (!full && !in.n_extra && in.ntxn) {
-            if (rp) {  // (the partitioned search's kernels: the diffs)
-                CK(g.diff.ensure(4 * ((size_t)in.ntxn + 2)));
-                CK(hipMemsetAsync(g.diff.p, 0, 4 * ((size_t)in.ntxn + 2), s));
-                diff = g.diff.as<uint32_t>();
-                diff_done = true;
-            } else {  // the rows themselves (the counter: g.count's u32 29, cleared by k_graph_meta)
-                // (HSC_GRAPH_BACK_CAP: a smaller list, read per build -- the
-                // tests' way to the diff fallback)
-                uint32_t cap = kBackCap;
-                if (const char *v = getenv("HSC_GRAPH_BACK_CAP")) cap = std::min<uint32_t>(kBackCap, (uint32_t)atoi(v));
-                CK(g.back.ensure(8 * (size_t)std::max<uint32_t>(cap, 1)));
-                sink = BackSink{nullptr, g.back.as<uint64_t>(), g.count.as<uint32_t>() + 29, cap};
-                g.back_cap = cap;
-                back_listed = true;
-            }
+            // (HSC_GRAPH_BACK_CAP: a smaller list, read per build -- the
+            // tests' way to the diff fallback)
+            uint32_t cap = kBackCap;
+            if (const char *v = getenv("HSC_GRAPH_BACK_CAP")) cap = std::min<uint32_t>(kBackCap, (uint32_t)atoi(v));
+            CK(g.back.ensure(8 * (size_t)std::max<uint32_t>(cap, 1)));
+            sink = BackSink{nullptr, g.back.as<uint64_t>(), g.count.as<uint32_t>() + 29, cap};
+            g.back_cap = cap;
+            back_listed = true;
         }
-        if (rp) {
-            RpArgs a{};
-            a.nops = nops, a.txn = in.txn, a.key = in.key, a.is_write = in.is_write, a.observed = in.observed;
-            a.nu = nu, a.wkey = wkey, a.wtxn = wtxn, a.pk = pkv, a.dir = g.pdir.as<uint32_t>();
-            a.ps = pp.D > kRpBitsMax ? (uint32_t)(pp.D - kRpBitsMax) : 0;
-            a.np = (uint32_t)((((uint64_t)1 << pp.D) >> a.ps) + 1);
-            CK(g.rp_cnt.ensure(8 * ((size_t)a.np + 2)));
-            a.cnt = g.rp_cnt.as<uint32_t>();
-            a.cur = a.cnt + a.np + 1;
-            CK(g.rp_items.ensure(16 * std::max<size_t>(nops, 1)));
-            a.items = g.rp_items.as<ulonglong2>();
-            a.ew = g.ew.as<uint64_t>(), a.et = et, a.eg = eg, a.skip_rw = in.skip_rw ? 1 : 0;
-            a.diff = diff;
-            CK(hipMemsetAsync(a.cnt, 0, 4 * ((size_t)a.np + 1), s));
-            k_rp_count<<<blocks(nops), kRpThreads, 0, s>>>(a, pp);
-            k_rp_scan<<<1, 1024, 0, s>>>(a);
-            k_rp_scatter<<<blocks(nops), kRpThreads, 0, s>>>(a, pp);
-            k_rp_join<<<a.np, kRpThreads, 0, s>>>(a, pp);
-            CK(hipGetLastError());
-            uint32_t tot[2];
-            CK(hipMemcpyAsync(&tot[0], a.cnt + a.np, 4, hipMemcpyDeviceToHost, s));
-            CK(hipMemcpyAsync(&tot[1], a.cur + a.np, 4, hipMemcpyDeviceToHost, s));
-            CK(hipStreamSynchronize(s));
-            rw_rows = (size_t)tot[0] + tot[1];
-            slot_layout = true;
-        } else if (pt && pp.shift <= 31) {  // (a bucket's offsets fit 32 bits)
+        if (pp.shift <= 31) {  // bucket lines (a bucket's offsets fit 32 bits)
             const uint64_t nb = ((uint64_t)1 << pp.D) + 1;
-            CK(g.ptab.ensure(8 * (size_t)kLine * nb));
-            // (HSC_GRAPH_NT=0: cached op loads and row stores, an A/B)
-            static const bool nt = getenv("HSC_GRAPH_NT") == nullptr || atoi(getenv("HSC_GRAPH_NT")) != 0;
-#define HSC_PT(LW_, NT_)                                                                                  \
-    k_pair_table<LW_><<<blocks(LW_ * nb), 256, 0, s>>>(nu, pkv, g.pdir.as<uint32_t>(), nb, pp,              \
-                                                       g.ptab.as<uint64_t>());                             \
-    k_edges_reads_pt<LW_, NT_><<<blocks(nops), 256, 0, s>>>(nops, in.txn, in.key, in.is_write, in.observed, \
-                                                            nu, wkey, wtxn, pkv, g.ptab.as<uint64_t>(), pp, \
-                                                            g.ew.as<uint64_t>(), et, eg, in.skip_rw ? 1 : 0, \
-                                                            sink, chk_n, ebad)
-            if (kLine == 16) {
-                HSC_PT(16, false);
-            } else if (nt) {
-                HSC_PT(8, true);
-            } else {
-                HSC_PT(8, false);
-            }
-#undef HSC_PT
-        } else {
+            CK(g.ptab.ensure(8 * (size_t)kPtLine * nb));
+            k_pair_table<<<blocks(kPtLine * nb), 256, 0, s>>>(nu, pkv, g.pdir.as<uint32_t>(), nb, pp,
+                                                              g.ptab.as<uint64_t>());
+            k_edges_reads_pt<<<blocks(nops), 256, 0, s>>>(nops, in.txn, in.key, in.is_write, in.observed, nu,
+                                                          wkey, wtxn, pkv, g.ptab.as<uint64_t>(), pp,
+                                                          g.ew.as<uint64_t>(), et, eg, in.skip_rw ? 1 : 0,
+                                                          sink, chk_n, ebad);
+        } else {  // the directory + pk search
             k_edges_reads_pk<<<blocks(nops), 256, 0, s>>>(nops, in.txn, in.key, in.is_write, in.observed, nu,
                                                           wkey, wtxn, pkv, g.pdir.as<uint32_t>(),
                                                           pp, g.ew.as<uint64_t>(), et, eg, in.skip_rw ? 1 : 0,
@@ -1313,8 +1047,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
                                                    in.skip_rw ? 1 : 0, chk_n, ebad);
     }
     CK(hipGetLastError());
-    // the partitioned search filled [nu, nu + nops + rw_rows) (else [nu, nu + 2 nops))
-    const size_t ne_hist = slot_layout ? (size_t)nu + nops + rw_rows : (size_t)nu + 2 * nops;
+    const size_t ne_hist = (size_t)nu + 2 * nops;
     const size_t ne_raw = ne_hist + in.n_extra;
     if (in.n_extra) {  // staged edges (rw pairs of the validator's join) after the history's
         const size_t o = ne_hist;
@@ -1326,10 +1059,9 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     }
     g.raw = !full;
     g.ne_raw = ne_raw;
-    g.op_cut = !full && !slot_layout && txn_sorted;
+    g.op_cut = !full && txn_sorted;
     g.op_at = nu, g.op_n = nops, g.x_at = ne_hist, g.x_n = in.n_extra;
-    g.diff_nn = diff_done ? in.ntxn : 0;  // graph_cover: the diffs are there already
-    g.back_listed = back_listed;          // graph_cover: the backward rows (count: graph_build_timed)
+    g.back_listed = back_listed;  // graph_cover: the backward rows (count: graph_build_timed)
     g.back_n = 0;
     g.cover_nn = in.ntxn;
     if (!full) {  // raw edge rows only (duplicates, ~0 holes): enough for cover / cut
@@ -1645,12 +1377,9 @@ hipError_t graph_cover(GraphBufs &g, uint32_t nn, uint8_t *cover, hipStream_t s)
     if ((e = diff.ensure(4 * ((size_t)nn + 2))) != hipSuccess) return e;
     if ((e = scratch.ensure(std::max(scan_scratch_bytes((size_t)nn + 1), (size_t)1024))) != hipSuccess)
         return e;
-    if (!(g.raw && g.diff_nn == nn)) {  // (a raw build accumulated them while emitting its rows)
-        if ((e = hipMemsetAsync(diff.p, 0, 4 * ((size_t)nn + 2), s)) != hipSuccess) return e;
-        const EdgeSet es = edge_set(g);
-        if (es.n) k_back_diff<<<blocks(es.n), 256, 0, s>>>(es, diff.as<uint32_t>());
-    }
-    g.diff_nn = 0;  // (the scan below consumes them)
+    if ((e = hipMemsetAsync(diff.p, 0, 4 * ((size_t)nn + 2), s)) != hipSuccess) return e;
+    const EdgeSet es = edge_set(g);
+    if (es.n) k_back_diff<<<blocks(es.n), 256, 0, s>>>(es, diff.as<uint32_t>());
     if ((e = scan_exclusive_u32(diff.as<uint32_t>(), (size_t)nn + 1, scratch.as<uint32_t>(), s)) !=
         hipSuccess)
         return e;
@@ -1803,9 +1532,8 @@ hipError_t graph_cut(GraphBufs &g, const uint8_t *cover, size_t *m, hipStream_t 
         // by the covered txns' ops (config 4: 1179 covered of 16.7M txns --
         // the ww rows and ~7k op rows tested instead of all 233M rows), unless
         // the cover has more than kCoverListCap txns (then every row, below)
-        static const bool no_op_cut = getenv("HSC_GRAPH_NO_OP_CUT") != nullptr;  // (A/B)
         bool done = false;
-        if (op_txn && g.raw && g.op_cut && !no_op_cut && nn) {
+        if (op_txn && g.raw && g.op_cut && nn) {
             if ((e = g.cover_list.ensure(4 * (size_t)kCoverListCap)) != hipSuccess) return e;
             uint32_t *cnt = g.count.as<uint32_t>();  // [0] cut rows, [1] covered txns
             k_cover_list<<<blocks(nn), 256, 0, s>>>(nn, cover, g.cover_bits.as<uint64_t>(),

@@ -879,7 +879,6 @@ static int device_build(hsc_ctx *c, size_t n_in)
     w.levels = c->levels;
     // the narrow index before the summaries: its level-1 LSN maxima (one per
     // 16 rows) give the window's tile maxima, read instead of every row's LSN
-    // (HSC_NTMAX_REBUILD=1: from the LSNs, an A/B)
     bool tiles_on = false, tiles_fused = false;
     uint32_t *tiles_flag = c->d_count.as<uint32_t>() + 4;
     if (c->narrow) {
@@ -935,9 +934,8 @@ static int device_build(hsc_ctx *c, size_t n_in)
         }
         bt.stamp("narrow");
     }
-    static const bool tmax_rows = getenv("HSC_NTMAX_REBUILD") != nullptr;
     TmaxFrom wfrom;
-    if (c->narrow && !tmax_rows && c->nv.levels >= 2 && c->log2T >= 4) wfrom.lsn16 = c->nv.maxs + c->nv.off[1];
+    if (c->narrow && c->nv.levels >= 2 && c->log2T >= 4) wfrom.lsn16 = c->nv.maxs + c->nv.off[1];
     HIPCHK(c, build_summaries(w, c->d_gstart.as<uint32_t>(), c->d_gend.as<uint32_t>(), ng,
                               c->d_tmax.as<uint64_t>(), c->d_group_table.as<uint32_t>(),
                               c->d_table_max.as<uint64_t>(), c->d_sp_g.as<uint32_t>(),
@@ -976,12 +974,10 @@ static int device_build(hsc_ctx *c, size_t n_in)
         wn.gid = c->d_nzero.as<uint32_t>();
         wn.tmax = c->d_ntmax.as<uint64_t>();
         // (the window's LSNs over tiles as long or twice as long as the
-        // window's: its sparse table folded, HSC_NTMAX_REBUILD=1 rebuilds it
-        // from the LSNs, an A/B)
-        static const bool ntmax_rebuild = getenv("HSC_NTMAX_REBUILD") != nullptr;
+        // window's: its sparse table folded; else rebuilt from the LSNs)
         TmaxFrom from;
         const int tsh = wn.log2T - c->log2T;
-        if (!ntmax_rebuild && (tsh == 0 || tsh == 1) && wn.ntiles > 0 && c->ntiles > 0 && c->levels >= wn.levels)
+        if ((tsh == 0 || tsh == 1) && wn.ntiles > 0 && c->ntiles > 0 && c->levels >= wn.levels)
             from = TmaxFrom{c->d_tmax.as<uint64_t>(), c->ntiles, tsh};
         HIPCHK(c, build_summaries(wn, c->d_ngs.as<uint32_t>(), c->d_ngs.as<uint32_t>() + 1, 1,
                                   c->d_ntmax.as<uint64_t>(), nullptr, nullptr,
@@ -2616,10 +2612,8 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
         // blocks past the tiles for the hot tiles' overflow items: 512, or 2048
         // on a skewed window (the bucket table took log mode: Zipf keys crowd
         // a few tiles -- r03: config 5 one stream 83 -> 80 us with 2048, while
-        // config 2's idle extra blocks cost its overlapped batch); diagnostics:
-        // HSC_JOIN_EXTRA
-        static const int extra_env = getenv("HSC_JOIN_EXTRA") ? atoi(getenv("HSC_JOIN_EXTRA")) : 0;
-        const uint32_t extra = extra_env > 0 ? (uint32_t)extra_env : c->trad_log ? 2048u : 512u;
+        // config 2's idle extra blocks cost its overlapped batch)
+        const uint32_t extra = c->trad_log ? 2048u : 512u;
         HIPCHK(c, launch_join_t(work, ntl, wn.n, wn.ntiles, max_items, b->verdict, s, extra));
         if (tm) HIPCHK(c, hipEventRecord(c->ev[4], s));
         HIPCHK_RC(c, probe_delta(c, b->verdict));
@@ -2688,8 +2682,6 @@ static int probe_ctiles(hsc_ctx *c, const hsc_probe_batch *b, const ProbeView &p
         work.stamps = stamp_buf.as<uint64_t>();
     }
 #endif
-    static const int dbg = getenv("HSC_CT_DBG") ? atoi(getenv("HSC_CT_DBG")) : 0;
-    ct.dbg = dbg;
     const size_t had = c->w_vflags.bytes;
     HIPCHK(c, c->w_vflags.ensure((std::max<size_t>(b->n_txn, 1) + 15) & ~(size_t)15));
     if (c->w_vflags.bytes != had) HIPCHK(c, hipMemsetAsync(c->w_vflags.p, 0, c->w_vflags.bytes, s));
@@ -2870,7 +2862,7 @@ static int probe_tiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &w, c
     HIPCHK(c, c->w_bucket.ensure(4 * ((size_t)nt + 1)));
     HIPCHK(c, c->w_cursor.ensure(4 * ((size_t)nt + 1)));
     HIPCHK(c, c->w_items.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_recs.ensure(8 * (size_t)rec_stride(w.W) * 2 * std::max<uint32_t>(p.n, 1)));
+    HIPCHK(c, c->w_recs.ensure(8 * (size_t)rec_words(w.W) * 2 * std::max<uint32_t>(p.n, 1)));
     const uint32_t max_items = nt + (uint32_t)((2 * (size_t)p.n + kJoinChunk - 1) / kJoinChunk);
     HIPCHK(c, c->w_item_tile.ensure(4 * (size_t)max_items + 16));
     HIPCHK(c, c->w_item_desc.ensure(16 * (size_t)max_items + 16));

@@ -110,15 +110,6 @@ struct ProbeView {
 // meta = txn | lb << 32 | ub << 44 | kind << 62 ([lb, ub) = the probe's
 // group rows inside the tile).  2W+2 words -> 16-byte multiple.
 __host__ __device__ inline int rec_words(int W) { return 2 * W + 2; }
-#ifndef HSC_REC_PAD
-#define HSC_REC_PAD 0
-#endif
-// Record stride in u64: with HSC_REC_PAD records start on 64-byte sectors,
-// so a scattered record is written as whole sectors.
-__host__ __device__ inline int rec_stride(int W)
-{
-    return HSC_REC_PAD ? (rec_words(W) + 7) & ~7 : rec_words(W);
-}
 
 constexpr int kMaxTileRows = 4096;  // window capacity is a multiple of this
 
@@ -527,13 +518,11 @@ struct GraphBufs {
     DBuf x_rows, x_type, x_map;                // staged extra edges (rw pairs)
     DBuf pk, pdir;                             // packed distinct writers + their directory
     DBuf ptab;                                 // the directory's buckets inline, one line each
-    DBuf rp_cnt, rp_items;                     // partitioned read search: counts / cursors, items
     size_t n_extra = 0;
     size_t ne = 0;
     size_t ne_raw = 0;  // raw edge slots in ew
     bool raw = false;   // last build kept raw rows only (no sort / CSR)
     bool writer_packed = false;  // last build sorted its writers as packed (key, txn) words
-    uint32_t diff_nn = 0;        // raw build: diff holds the cover's backward-edge diffs over diff_nn txns
     uint32_t cover_nn = 0;       // txns of the covers graph_cut tests (the build's ntxn)
     uint32_t bad = 0;            // the last checked build's input bits (GraphInput::check)
     uint32_t *edge_bad = nullptr;  // device word of the edge pass's observed-id check (graph_build_timed
@@ -562,8 +551,8 @@ struct GraphBufs {
                        &ew, &et, &eg, &ew2, &et2, &eg2, &swap_rows, &src, &out_dst, &type,
                        &in_src, &in_dst, &out_off, &in_off, &scc, &active, &color, &mark,
                        &front, &front2, &h_txn, &h_key, &h_isw, &h_obs, &diff, &cut,
-                       &cut_id, &txn_of, &x_rows, &x_type, &x_map, &pk, &pdir, &ptab, &rp_cnt,
-                       &rp_items, &cover_bits, &cover_list, &gvary, &back};
+                       &cut_id, &txn_of, &x_rows, &x_type, &x_map, &pk, &pdir, &ptab,
+                       &cover_bits, &cover_list, &gvary, &back};
         for (DBuf *b : all) b->release();
     }
 };
@@ -646,7 +635,6 @@ struct CTiles {
     int WG, WC, gb;          // key words, code words, group bits
     uint32_t np;             // probes of the batch
     uint32_t *recs;          // chunk areas of 2 x chunk 64-byte records (k_locate_c)
-    int dbg;                 // diagnostics (HSC_CT_DBG): 1 join skips the searches, 2 also the gathers
 };
 // Exact-key index of the compact tiles' keys for point probes (lo == hi):
 // open addressing over 128-byte buckets of four 32-byte entries {key words

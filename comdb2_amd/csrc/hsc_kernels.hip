@@ -24,7 +24,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <utility>
 
 namespace hsc {
@@ -128,11 +127,12 @@ __global__ __launch_bounds__(256) void k_vary_mask(int W, size_t n, const uint32
 // row's words, gid and LSN are loaded together (U rows per thread, all loads
 // in flight before the first OR).  k_vary_mask above walks the rows once per
 // word: 100 us for config 2's 280 MB (2.8 TB/s).
-template <int WT, int U = 8>
+template <int WT>
 __global__ __launch_bounds__(256) void k_vary_mask_w(size_t n, const uint32_t *gid, const uint64_t *words,
                                                      size_t stride, const uint64_t *lsn,
                                                      unsigned long long *mask)
 {
+    constexpr int U = 8;
     __shared__ uint64_t part[256 / 64][WT + 4];
     uint64_t ref[WT + 1], m[WT + 1];
 #pragma unroll
@@ -450,17 +450,10 @@ hipError_t vary_mask_rows(int W, size_t n, const uint32_t *gid, const uint64_t *
     // workgroups OR into the same W + 3 words, one atomic each per word (2048
     // workgroups of 4 rows measured 109 us on config 2, the per-word kernel
     // 100 us)
-    static const size_t vary_wg = getenv("HSC_VARY_WG") ? (size_t)atoi(getenv("HSC_VARY_WG")) : 512;  // (A/B)
-    static const int vary_u = getenv("HSC_VARY_U") ? atoi(getenv("HSC_VARY_U")) : 8;  // rows per thread (A/B: 16)
-    const unsigned wgrid = (unsigned)std::min<size_t>((n + 2047) / 2048, std::max<size_t>(vary_wg, 1));
+    const unsigned wgrid = (unsigned)std::min<size_t>((n + 2047) / 2048, 512);
     switch (W) {
     case 1: k_vary_mask_w<1><<<wgrid, 256, 0, s>>>(n, gid, words, stride, ls, dmask); break;
-    case 2:
-        if (vary_u == 16)
-            k_vary_mask_w<2, 16><<<wgrid, 256, 0, s>>>(n, gid, words, stride, ls, dmask);
-        else
-            k_vary_mask_w<2><<<wgrid, 256, 0, s>>>(n, gid, words, stride, ls, dmask);
-        break;
+    case 2: k_vary_mask_w<2><<<wgrid, 256, 0, s>>>(n, gid, words, stride, ls, dmask); break;
     case 3: k_vary_mask_w<3><<<wgrid, 256, 0, s>>>(n, gid, words, stride, ls, dmask); break;
     case 4: k_vary_mask_w<4><<<wgrid, 256, 0, s>>>(n, gid, words, stride, ls, dmask); break;
     default: {
@@ -1055,7 +1048,7 @@ __device__ __forceinline__ void write_record(const WinView &w, uint64_t *recs, u
     const uint64_t lb = gs > ts ? min(gs - ts, tn) : 0;
     const uint64_t ub = ge > ts ? min(ge - ts, tn) : 0;
     const uint64_t meta = (uint64_t)p.txn[q] | (lb << 32) | (ub << 45) | (kind << 62);
-    ulonglong2 *r = (ulonglong2 *)(recs + (size_t)slot * rec_stride(W));
+    ulonglong2 *r = (ulonglong2 *)(recs + (size_t)slot * rec_words(W));
     const size_t ks = p.n;
     auto word = [&](int k) -> uint64_t {
         if (k < W) return p.lo[(size_t)k * ks + q];
@@ -1126,7 +1119,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_scatter(WinView w, ProbeView
     const uint32_t c1 = min(p.n, c0 + work.chunk);
     const size_t ks = p.n;
     const uint32_t T = 1u << w.log2T;
-    constexpr int rs = HSC_REC_PAD ? 8 : 2 * WT + 2;
+    constexpr int rs = 2 * WT + 2;
     for (uint32_t base = c0; base < c1; base += kScatB * kLocateThreads) {
         constexpr int WA = WT > 2 ? WT : 2;
         uint64_t cd[kScatB], lo[kScatB][WA], hi[kScatB][WA], snap[kScatB];
@@ -1256,7 +1249,7 @@ __global__ __launch_bounds__(kJoinThreads) void k_join(WinView w, ProbeWork work
     const uint32_t rb = work.bucket_off[tile] + (item - work.item_off[tile]) * kJoinChunk;
     const uint32_t re = min(rb + (uint32_t)kJoinChunk, work.bucket_off[tile + 1]);
     const int W = WT > 0 ? WT : w.W;
-    const int rw = rec_stride(W);
+    const int rw = rec_words(W);
     const uint32_t T = 1u << w.log2T;
     const uint32_t ts = tile << w.log2T;
 

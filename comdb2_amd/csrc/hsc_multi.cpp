@@ -614,10 +614,8 @@ static int probe_merge(hsc_ctx *f, int L, hsc_probe_batch *in, const size_t *tb,
     };
     int prc[kMultiMax] = {};
     const auto tp0 = SteadyClock::now();
-    // (members sharing a GPU: one thread -- its launches serialise anyway;
-    // HSC_MULTI_PAR_LAUNCH=1 issues them from the pool there too, an A/B)
-    static const bool par_env = getenv("HSC_MULTI_PAR_LAUNCH") != nullptr;
-    if (M->ndev > 1 || (par_env && NL > 1))
+    // (members sharing a GPU: one thread -- its launches serialise anyway)
+    if (M->ndev > 1)
         ctx_par_for(f, NL, [&](int m) { prc[m] = probe_one(m); });
     else
         for (int m = 0; m < NL; ++m) prc[m] = probe_one(m);

@@ -33,7 +33,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace hsc {
 
@@ -377,18 +376,16 @@ __global__ void k_level_up(const uint64_t *key_src, const uint64_t *max_src, uin
 
 bool narrow_level01_tiles(const NarrowView &nv)
 {
-    static const bool sep = getenv("HSC_LEVEL_SEP") != nullptr;
-    return !sep && nv.levels >= 2 && nv.len[0] % (1u << kTLog2) == 0;
+    return nv.levels >= 2 && nv.len[0] % (1u << kTLog2) == 0;
 }
 
 hipError_t narrow_build(const WinView &w, const NarrowView &nv, hipStream_t s, uint32_t *key32,
                         uint32_t *rank32, uint64_t rank_base, uint32_t *flag)
 {
     const uint32_t len0 = nv.len[0];
-    static const bool sep = getenv("HSC_LEVEL_SEP") != nullptr;  // (A/B: level 1 by its own pass)
     int l = 1;
     if (key32 && !narrow_level01_tiles(nv)) return hipErrorInvalidValue;
-    if (nv.levels >= 2 && len0 % 256 == 0 && !sep) {
+    if (nv.levels >= 2 && len0 % 256 == 0) {
         if (key32) {
             const hipError_t e = hipMemsetAsync(flag, 0, 4, s);
             if (e != hipSuccess) return e;
@@ -1249,19 +1246,10 @@ __global__ __launch_bounds__(kRankThreads) void k_rank32(const uint64_t *lsn, ui
 // search and the tiles' first codes never leave LDS).  Output per probe: its
 // first join record {tile << 12 | rank, lo, hi, r(S)} and, for a range that
 // spans two tiles, its second one.
-#ifndef HSC_LOC_TP
-#define HSC_LOC_TP 4
-#endif
-#ifndef HSC_DIR_LDS
-#define HSC_DIR_LDS 4400
-#endif
-constexpr int kLocTP = HSC_LOC_TP;
-#ifndef HSC_LOC_THREADS
-#define HSC_LOC_THREADS 1024
-#endif
-constexpr int kLocTThreads = HSC_LOC_THREADS;  // <= 4096 probes per chunk (in-chunk ranks fit 12 bits)
+constexpr int kLocTP = 4;
+constexpr int kLocTThreads = 1024;  // <= 4096 probes per chunk (in-chunk ranks fit 12 bits)
 static_assert(kLocTP * kLocTThreads <= 4096, "in-chunk ranks are 12 bits");
-constexpr int kDirLds = HSC_DIR_LDS;  // directory entries staged in LDS per directory
+constexpr int kDirLds = 4400;  // directory entries staged in LDS per directory
 
 template <int W>
 __device__ __forceinline__ void locate_codes(const NarrowView &nv, const ProbeView &p, uint32_t q,
@@ -1443,27 +1431,18 @@ struct LocDefer {
 };
 
 // W = key words held in registers (1 or 2), 0 = read from memory (any W).
-// The chunk's kLocTP probes per thread run as kLocTP / kLocSub sub-chunks of
-// kLocSub probes per thread: the loads of sub-chunk s + 1 are in flight while
-// sub-chunk s is located (codes, snapshot ranks, end tiles, records), so the
-// chunk's HBM reads overlap its LDS / VALU work instead of preceding it.
-#ifndef HSC_LOC_SUB  // (r02, chunk-sorted records: 1 probe per sub-chunk 2.10 G vs 2 probes 2.00 G)
-#define HSC_LOC_SUB 1
-#endif
-constexpr int kLocSub = HSC_LOC_SUB;
-#ifndef HSC_LOC_WPE
-#define HSC_LOC_ATTR
-#else  // A/B builds: hold the locate to HSC_LOC_WPE waves per SIMD
-#define HSC_LOC_ATTR __attribute__((amdgpu_waves_per_eu(HSC_LOC_WPE, HSC_LOC_WPE)))
-#endif
-static_assert(kLocTP % kLocSub == 0, "whole sub-chunks");
+// The chunk's kLocTP probes per thread run as kLocTP sub-chunks of one probe
+// per thread: the loads of sub-chunk s + 1 are in flight while sub-chunk s is
+// located (codes, snapshot ranks, end tiles, records), so the chunk's HBM
+// reads overlap its LDS / VALU work instead of preceding it.  (r02,
+// chunk-sorted records: 1 probe per sub-chunk 2.10 G vs 2 probes 2.00 G.)
 template <int W, bool kTrad>
-__global__ __launch_bounds__(kLocTThreads) HSC_LOC_ATTR void k_locate_t(NarrowView nv, WinView wt,
-                                                             ProbeView p, ProbeWork work,
-                                                             NarrowTiles nt, uint8_t *verdict)
+__global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinView wt, ProbeView p,
+                                                           ProbeWork work, NarrowTiles nt,
+                                                           uint8_t *verdict)
 {
     constexpr int WR = 2 > W ? 2 : W;
-    constexpr int K = kLocSub, S = kLocTP / kLocSub;
+    constexpr int K = 1, S = kLocTP;  // probes per sub-chunk and thread, sub-chunks
     extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
     const uint32_t ntiles = wt.ntiles;
     const LocLds L = loc_lds(nt, ntiles);
@@ -1766,7 +1745,7 @@ uint32_t narrow_tiles_dir_lds() { return kDirLds; }
 
 // ---- plan ----
 // ctl[1] (extra join items) was zeroed by this batch's locate.
-// Plan of chunk-sorted records: block = 8 tiles (HSC_PLAN_S_THREADS / 64).
+// Plan of chunk-sorted records: block = 8 tiles (kPlanSThreads / 64).
 // The block reads the tiles' entries of every chunk row of the locate's
 // chunk-major table (32 contiguous bytes per row), transposes them through LDS, and wave w scans
 // tile t0 + w's column as k_plan_t does; it writes the tile-major exclusive
@@ -1776,10 +1755,7 @@ uint32_t narrow_tiles_dir_lds() { return kDirLds; }
 // 512 threads (8 tiles, 32-byte row pieces) vs 1024 (16 tiles, 64-byte
 // pieces): one stream 62.1 vs 61.1 us, two streams 2.22 vs 2.17 G checks/s
 // (r02d) -- the headline is the two-stream number
-#ifndef HSC_PLAN_S_THREADS
-#define HSC_PLAN_S_THREADS 512
-#endif
-constexpr int kPlanSThreads = HSC_PLAN_S_THREADS;  // a wave per tile
+constexpr int kPlanSThreads = 512;  // a wave per tile
 __global__ __launch_bounds__(kPlanSThreads) void k_plan_s(ProbeWork work, uint32_t ntiles,
                                                           uint32_t *ctl, uint8_t *flags,
                                                           uint32_t n_txn, uint8_t *verdict)
@@ -1877,10 +1853,6 @@ hipError_t launch_plan_s(const ProbeWork &work, uint32_t ntiles, uint32_t *ctl, 
 
 // The join is held to 8 waves per SIMD: at 85-99 SGPRs the hardware admits
 // only 6-7 (measured on config 2: join 34 -> 31.7 us, one stream 71.3 -> 69 us)
-#ifndef HSC_JOIN_WPE
-#define HSC_JOIN_WPE 8
-#endif
-#define HSC_JOIN_ATTR __attribute__((amdgpu_waves_per_eu(HSC_JOIN_WPE, HSC_JOIN_WPE)))
 // Chunk-sorted records: record j of tile t lives in the
 // run of the chunk g whose offset inside the tile (the plan's scan of column
 // t) is the last one <= j, at chunk g's area + cst[t][g] + (j - that offset).
@@ -1978,18 +1950,12 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
     }
 }
 
-#ifndef HSC_JOIN_XCD  // (r02c: config 2 2.09 -> 2.16 G checks/s, join 31.7 -> 29.6 us)
-#define HSC_JOIN_XCD 1
-#endif
-constexpr bool kJoinXcd = HSC_JOIN_XCD != 0;
-__host__ __device__ inline uint32_t join_tile_blocks(uint32_t ntiles)
-{
-    return kJoinXcd ? 8 * ((ntiles + 7) / 8) : ntiles;
-}
+// the tiles' blocks, a multiple of 8: tile = xcd_chunk(block) (r02c: config 2
+// 2.09 -> 2.16 G checks/s, join 31.7 -> 29.6 us against tile = block)
+__host__ __device__ inline uint32_t join_tile_blocks(uint32_t ntiles) { return 8 * ((ntiles + 7) / 8); }
 
-__global__ __launch_bounds__(kJoinThreads) HSC_JOIN_ATTR void k_join_t(ProbeWork work, NarrowTiles nt,
-                                                         uint32_t n, uint32_t ntiles,
-                                                         uint8_t *verdict)
+__global__ __launch_bounds__(kJoinThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_join_t(
+    ProbeWork work, NarrowTiles nt, uint32_t n, uint32_t ntiles, uint8_t *verdict)
 {
     constexpr uint32_t T = 1u << kTLog2;
     __shared__ __attribute__((aligned(16))) uint32_t keys[T];
@@ -2003,7 +1969,7 @@ __global__ __launch_bounds__(kJoinThreads) HSC_JOIN_ATTR void k_join_t(ProbeWork
     // chunk share lines of its record area, which that XCD's L2 then serves)
     const uint32_t tb = join_tile_blocks(ntiles);
     if (blockIdx.x < tb) {
-        const uint32_t tile = kJoinXcd ? xcd_chunk(blockIdx.x, tb / 8) : blockIdx.x;
+        const uint32_t tile = xcd_chunk(blockIdx.x, tb / 8);
         if (tile < ntiles) join_s_item<true>(work, nt, n, tile, verdict, keys, rank, b16, b128, Es, Cs);
     } else {  // blocks past the tiles take the hot tiles' overflow items in turn
         const uint32_t nextra = work.item_off[1];

@@ -298,6 +298,53 @@ def test_gpu_multi_graph_scc_build_paths(oracle_mod, case, monkeypatch):
     np.testing.assert_array_equal(_multi_scc(h, world=2), want)
 
 
+def _read_search_history(key_bits):
+    """2000 txns, ~12k ops over ~2700 distinct keys in [0, 2^12) (a mild Zipf:
+    its hot keys make wr, ww and rw edges among the concurrent txns and ~90
+    multi-txn components), key id i mapped to a distinct value uniform over
+    key_bits bits (12: the ids themselves)."""
+    from comdb2_amd.workloads import History
+    h = config4_history(seed=21, n_txn=2000, n_keys=1 << 12, concurrent_frac=0.3, max_lag=16, zipf=0.1)
+    if key_bits == 12:
+        return h
+    hi = (1 << key_bits) - 1
+    vals = np.random.default_rng(key_bits).integers(0, hi, size=1 << 12, dtype=np.uint64, endpoint=True)
+    assert len(np.unique(vals)) == len(vals)
+    return History(h.txn, vals[h.key.astype(np.int64)], h.is_write, h.observed, h.ntxn)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key_bits", [12, 45, 64])
+def test_gpu_multi_graph_scc_read_searches(oracle_mod, key_bits):
+    """The three read searches of a raw graph_build, each reached by the width
+    of the keys alone.  The writers' varying key bits are all key_bits of them,
+    their txns vary in 11 bits, and the ~3.9k distinct writers get D = 9
+    directory bits (the first D with 8 << D >= their count):
+    12 bits -- the writers pack (12 + 11 <= 64) into a range below 2^23, so a
+        bucket spans 2^shift packed values with shift <= 23 - 9 = 14 <= 31: the
+        bucket lines (k_pair_table + k_edges_reads_pt);
+    45 bits -- they pack (45 + 11 = 56 <= 64) into a range of 2^55 .. 2^56
+        (the writers' keys span more than 2^44), so shift >= 55 - 9 = 46 > 31
+        and a bucket's 32-bit offsets do not fit: the directory + packed-key
+        search (k_edges_reads_pk);
+    64 bits -- 64 + 11 varying bits do not fit a word: the whole-row sort and
+        the row search (k_edges_reads).
+    Components = Tarjan's over the whole history, one member and two."""
+    h = _read_search_history(key_bits)
+    w = h.is_write != 0
+    vary = int(np.bitwise_or.reduce(h.key[w]) & ~np.bitwise_and.reduce(h.key[w]))
+    assert bin(vary).count("1") == key_bits  # (every bit of the width varies among the writers)
+    nu = len(np.unique(np.stack([h.key[w], h.txn[w].astype(np.uint64)], 1), axis=0))
+    assert 2048 < nu <= 4096  # D = 9 (8 with the writers split over two members: shift + 1)
+    assert key_bits == 12 or int(h.key[w].max() - h.key[w].min()) >> (key_bits - 1) == 1  # the span
+    s, d, t = oracle_mod.dep_edges(h.txn, h.key, h.is_write, h.observed)
+    assert int(np.bitwise_or.reduce(t)) == 7  # ww | wr | rw
+    want = oracle_mod.scc(h.ntxn, s, d)
+    assert np.bincount(want, minlength=h.ntxn).max() > 1  # a multi-txn component
+    np.testing.assert_array_equal(_multi_scc(h), want)
+    np.testing.assert_array_equal(_multi_scc(h, world=2), want)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("field", ["read_observed", "write_observed", "txn"])
 def test_gpu_multi_graph_scc_rejects_ids_out_of_range(field):

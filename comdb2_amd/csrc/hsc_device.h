@@ -279,6 +279,73 @@ __device__ __forceinline__ bool any_after32(const uint32_t *rank, const uint32_t
     return r;
 }
 
+// any_after32 for a whole wave (call it in wave-uniform control flow; live =
+// this lane has a non-empty range [p, q), p, q <= 4096).  The two-read filter
+// stays per lane and decides most ranges; the ranges it leaves are resolved
+// four per pass, one per 16-lane group: the group gets the range by __shfl and
+// covers the slots any_after32 reads under the same guards -- a short range's
+// rows in one read per lane; of a long one the head and tail rows (<= 15
+// each, one read each), the two b16 pieces (<= 7 each, lanes 0-7 / 8-15) and
+// b128 (<= 32, two per lane) -- and one ballot hands the four 16-bit results
+// back to the owners.  A pass runs for a few of the wave's lanes' ranges at
+// once where the per-lane loops ran the longest lane's count with the other
+// lanes idle.
+__device__ __forceinline__ bool wave_any_after32(const uint32_t *rank, const uint32_t *b16,
+                                                 const uint32_t *b128, uint32_t p, uint32_t q,
+                                                 uint32_t s, bool live)
+{
+    const uint32_t lane = __lane_id(), grp = lane >> 4, l = lane & 15;
+    const uint32_t q1 = q - 1;
+    const bool hot_p = live & (b16[live ? p >> 4 : 0] > s);
+    const bool hot_q = live & (b16[live ? q1 >> 4 : 0] > s);
+    const bool pend = live && (hot_p || hot_q || (q1 >> 4) > (p >> 4) + 1);
+    const uint32_t pk = p | q << 13 | (uint32_t)hot_p << 26 | (uint32_t)hot_q << 27;
+    bool hit = false;
+    uint64_t m = __ballot(pend);
+    while (m) {  // wave-uniform
+        // group g takes the g-th pending lane
+        uint64_t t = m;
+        int src = -1;
+#pragma unroll
+        for (uint32_t g = 0; g < 4; ++g) {
+            const int b = __ffsll((unsigned long long)t) - 1;
+            if (grp == g) src = b;
+            t &= t - 1;
+        }
+        const bool on = src >= 0;
+        const uint32_t K = (uint32_t)__shfl((int)pk, on ? src : 0, 64);
+        const uint32_t S = (uint32_t)__shfl((int)s, on ? src : 0, 64);
+        const uint32_t P = K & 0x1FFFu, Q = K >> 13 & 0x1FFFu;
+        const bool HP = K >> 26 & 1, HQ = K >> 27 & 1;
+        const bool lng = on && Q - P > 16;
+        const uint32_t p16 = (P + 15) & ~15u, q16 = Q & ~15u;
+        // a short range's rows, a long one's head rows [P, p16)
+        const uint32_t i0 = P + l;
+        const bool c0 = on && (lng ? HP && i0 < p16 : i0 < Q);
+        bool r = c0 & (rank[c0 ? i0 : 0] > S);
+        if (__ballot(lng)) {
+            const uint32_t bp = p16 >> 4, bq = q16 >> 4;
+            const uint32_t bp8 = min((bp + 7) & ~7u, bq), bq8 = max(bq & ~7u, bp8);
+            const uint32_t i1 = q16 + l;  // tail rows [q16, Q)
+            const bool c1 = lng && HQ && i1 < Q;
+            const uint32_t i2 = l < 8 ? bp + l : bq8 + (l - 8);  // b16 [bp, bp8), [bq8, bq)
+            const bool c2 = lng && i2 < (l < 8 ? bp8 : bq);
+            const uint32_t i3 = (bp8 >> 3) + l, i4 = i3 + 16, e3 = bq8 >> 3;  // b128
+            const bool c3 = lng && i3 < e3, c4 = lng && i4 < e3;
+            const uint32_t v1 = rank[c1 ? i1 : 0], v2 = b16[c2 ? i2 : 0];
+            const uint32_t v3 = b128[c3 ? i3 : 0], v4 = b128[c4 ? i4 : 0];
+            r |= (c1 & (v1 > S)) | (c2 & (v2 > S)) | (c3 & (v3 > S)) | (c4 & (v4 > S));
+        }
+        const uint64_t hb = __ballot(r);
+        // the n-th pending lane owns group n's 16 result bits
+        const uint32_t nth = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        if ((m >> lane & 1) && nth < 4) hit = (hb >> (16 * nth) & 0xFFFFu) != 0;
+        m = t;  // less the four taken
+    }
+    return hit;
+}
+
 // Block-uniform load through the constant address space: a scalar load,
 // counted apart from the vector loads (waiting for it drains none of them).
 template <class T>

@@ -1927,7 +1927,9 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
 #pragma unroll
     for (int k = 0; k < kRec; ++k) {
         const uint32_t j = j0 + k * kJoinThreads + threadIdx.x;
-        if (j >= j1) continue;
+        // a wave past the item's records skips the round as a whole; inside,
+        // j < j1 is a predicate (the range maxima are resolved by the wave)
+        if (__builtin_amdgcn_readfirstlane(j) >= j1) continue;
         const uint32_t lo = rec[k].x, hi = rec[k].y, rs = rec[k].z;
         uint32_t ja = 1, jb = 1;
 #pragma unroll
@@ -1939,7 +1941,7 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
         const uint32_t kl = keys[0];
         const uint32_t pa = min(ja - T + (kl < lo), tn);
         const uint32_t pb = min(jb - T + (kl <= hi), tn);
-        if (pa < pb && any_after32(rank, b16, b128, pa, pb, rs)) {
+        if (wave_any_after32(rank, b16, b128, pa, pb, rs, j < j1 && pa < pb)) {
             // (r05w, world-1 per-rank step: these atomics 50.7 / 51.9 us per
             // step, guarded by a read of the verdict byte 53.3 / 52.5, the
             // pack pass instead 52.7 / 51.9 -- the same within the spread)

@@ -661,6 +661,8 @@ struct hsc_ctx {
     GraphBufs subgraph;  // the graph induced on a cover (sharded SCC)
     uint32_t graph_ntxn = 0;
     uint32_t x_max_txn = 0;  // largest txn id a staged rw pair can name (stage_rw_pairs)
+    AnomBufs anom;           // hsc_dep_graph_anomalies: device scratch, host results
+    AnomOut anom_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

@@ -3300,7 +3300,8 @@ int hsc_ctx_create(int device, hsc_ctx **out)
         if (warmed.size() < (size_t)n) warmed.resize(n, false);
         if (!warmed[device]) {
             for (auto f : {warm_kernels, warm_ingest, warm_narrow, warm_ctiles, warm_delta,
-                           warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_route})
+                           warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_anomaly,
+                           warm_route})
                 (void)f();
             warmed[device] = true;
         }
@@ -3373,6 +3374,7 @@ void hsc_ctx_destroy(hsc_ctx *c)
         if (L.done) (void)hipEventDestroy(L.done);
     }
     c->graph.release_all();
+    c->anom.release_all();
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -4770,6 +4772,54 @@ int hsc_dep_graph_scc_built(hsc_ctx *c, uint32_t *scc_out, hsc_graph_stats *st)
     }
     (void)hipEventDestroy(e1);
     (void)hipEventDestroy(e2);
+    return HSC_OK;
+}
+
+int hsc_dep_graph_anomalies(hsc_ctx *c, unsigned flags, unsigned max_anti_batches, hsc_anomalies *out)
+{
+    if (!c || !out) return HSC_EINVAL;
+    if (c->host_only) return HSC_EDEVICE;
+    MuGuard g(c);
+    (void)hipSetDevice(c->device);
+    GraphBufs &gb = c->graph;
+    const uint32_t nn = c->graph_ntxn;
+    if (gb.raw) return fail(c, HSC_ESTATE, "last build kept raw rows only (no HSC_GRAPH_FULL)");
+    hipStream_t s = c->stream;
+    hipEvent_t e1, e2;
+    HIPCHK(c, hipEventCreate(&e1));
+    HIPCHK(c, hipEventCreate(&e2));
+    HIPCHK(c, hipEventRecord(e1, s));
+    AnomOut &o = c->anom_out;
+    hipError_t e = graph_anomalies(nn, gb, c->anom, (flags & HSC_ANOM_WITNESS) != 0, max_anti_batches, o, s);
+    if (e == hipSuccess) e = hipEventRecord(e2, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    memset(out, 0, sizeof *out);
+    if (e == hipSuccess) (void)hipEventElapsedTime(&out->ms, e1, e2);
+    (void)hipEventDestroy(e1);
+    (void)hipEventDestroy(e2);
+    HIPCHK(c, e);
+    // (never a null array: an empty vector's data() may be)
+    static const uint8_t none8[1] = {0};
+    static const uint32_t none32[1] = {0};
+    out->ntxn = nn;
+    out->cls = o.cls.empty() ? none8 : o.cls.data();
+    out->ncomp = (uint32_t)o.comp_label.size();
+    out->comp_label = o.comp_label.empty() ? none32 : o.comp_label.data();
+    out->comp_class = o.comp_class.empty() ? none8 : o.comp_class.data();
+    if (o.wit_off.size() != (size_t)out->ncomp + 1) o.wit_off.assign((size_t)out->ncomp + 1, 0);
+    out->wit_off = o.wit_off.data();
+    out->wit_txn = o.wit_txn.empty() ? none32 : o.wit_txn.data();
+    out->wit_type = o.wit_type.empty() ? none8 : o.wit_type.data();
+    for (int k = 0; k < 3; ++k) {
+        out->comps[k] = o.comps[k];
+        out->txns[k] = o.txns[k];
+    }
+    out->anti_edges = o.anti_edges;
+    out->anti_tested = o.anti_tested;
+    out->core_nodes = o.core_nodes;
+    out->reach_batches = o.reach_batches;
+    out->sweeps = (uint32_t)std::min<uint64_t>(o.sweeps, 0xFFFFFFFFull);
+    out->bfs_levels = o.bfs_levels;
     return HSC_OK;
 }
 

@@ -568,6 +568,43 @@ hipError_t graph_pairs_rows(size_t n, const uint32_t *txn, const uint64_t *lsn, 
                             uint32_t *bad, hipStream_t s);
 hipError_t graph_scc(uint32_t nnodes, GraphBufs &g, uint32_t *rounds, uint32_t *iterations,
                      hipStream_t s);
+// Anomaly classes and witness cycles of a full build (hsc_anomaly.hip): the
+// analysis keeps its own buffers, so the build's edges and CSR stay as they
+// are (graph_scc's labels in g.scc are recomputed).
+struct AnomBufs {
+    DBuf flag, id, node_txn, root, cid, comp_of, comp_label;  // core nodes and components
+    DBuf eflag, epos, csrc, cdst, ctype, coff;                // core edges (typed CSR)
+    DBuf f1, fa, s1, e1i, aa, ab, ae, closed;                 // E1 rows, anti edges
+    DBuf F, B, gs, g1c, cg2, cls;                             // reach masks, per-node bits
+    DBuf wmin, wsrc, wtgt, wmask, pedge, target, front, front2;  // witness BFS
+    DBuf scratch, cnt;
+    GraphBufs e1;  // the core restricted to E1: CSR / CSC and graph_scc's arrays
+    void release_all();
+};
+struct AnomOut {  // host results (hsc_anomalies points into them)
+    std::vector<uint8_t> cls, comp_class, wit_type;
+    std::vector<uint32_t> comp_label, wit_off, wit_txn;
+    uint32_t comps[3], txns[3];
+    uint64_t anti_edges, anti_tested, sweeps;
+    uint32_t core_nodes, reach_batches, bfs_levels, scc_rounds, scc_iterations;
+    void clear(uint32_t ntxn)
+    {
+        cls.assign(ntxn, 0);
+        comp_class.clear();
+        wit_type.clear();
+        comp_label.clear();
+        wit_off.assign(1, 0);
+        wit_txn.clear();
+        for (int k = 0; k < 3; ++k) comps[k] = txns[k] = 0;
+        anti_edges = anti_tested = sweeps = 0;
+        core_nodes = reach_batches = bfs_levels = scc_rounds = scc_iterations = 0;
+    }
+};
+// max_batches: stop the G-single reach after that many batches of 64 anti
+// edges (0 = all; the bit is then a lower bound).  witness: one cycle per
+// component.
+hipError_t graph_anomalies(uint32_t nnodes, GraphBufs &g, AnomBufs &a, bool witness, uint32_t max_batches,
+                           AnomOut &out, hipStream_t s);
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {
@@ -839,6 +876,7 @@ hipError_t warm_compact();
 hipError_t warm_coalesce();
 hipError_t warm_edges();
 hipError_t warm_graph();
+hipError_t warm_anomaly();
 hipError_t warm_route();
 
 }  // namespace hsc

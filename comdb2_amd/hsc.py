@@ -108,6 +108,19 @@ class GraphStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+ANOM_G1C, ANOM_GSINGLE, ANOM_G2 = 1, 2, 4  # hsc_anomalies cls / comp_class bits
+ANOM_WITNESS = 1                           # hsc_dep_graph_anomalies flags
+
+
+class Anomalies(C.Structure):
+    """hsc_anomalies: the arrays are host memory of the context."""
+    _fields_ = [("ntxn", C.c_uint32), ("cls", _p), ("ncomp", C.c_uint32), ("comp_label", _p),
+                ("comp_class", _p), ("wit_off", _p), ("wit_txn", _p), ("wit_type", _p),
+                ("comps", C.c_uint32 * 3), ("txns", C.c_uint32 * 3), ("anti_edges", C.c_uint64),
+                ("anti_tested", C.c_uint64), ("core_nodes", C.c_uint32), ("reach_batches", C.c_uint32),
+                ("sweeps", C.c_uint32), ("bfs_levels", C.c_uint32), ("ms", C.c_float)]
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -178,6 +191,7 @@ EXPORTS = [
     "hsc_set_autocollect",
     "hsc_small_stats", "hsc_harness_concurrent",
     "hsc_dep_graph_build", "hsc_dep_graph_stage_rw_pairs", "hsc_dep_graph_scc_built", "hsc_dep_graph_build_device", "hsc_dep_graph_cover", "hsc_dep_graph_cut", "hsc_dep_graph_scc_cut",
+    "hsc_dep_graph_anomalies",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -262,6 +276,7 @@ def load() -> C.CDLL:
         "hsc_dep_graph_build_device": (C.c_int, [_p, C.c_size_t, C.c_uint32, _p, _p, _p, _p,
                                                  C.c_int, C.POINTER(GraphStats)]),
         "hsc_dep_graph_cut": (C.c_int, [_p, _p, _p, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "hsc_dep_graph_anomalies": (C.c_int, [_p, C.c_uint, C.c_uint, C.POINTER(Anomalies)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
         "hsc_window_ingest_raw": (C.c_int, [_p, C.POINTER(_RawLog)]),
@@ -1046,6 +1061,35 @@ class Validator:
                                                a[2].ctypes.data, m, C.byref(n)),
                   "hsc_dep_graph_edges")
         return tuple(x[:m] for x in a)
+
+    def dep_graph_anomalies(self, witness: bool = True, max_anti_batches: int = 0) -> dict:
+        """Anomaly classes of the last full build (hsc_dep_graph_anomalies):
+        cls[ntxn] (bits ANOM_G1C / ANOM_GSINGLE / ANOM_G2), comp_label /
+        comp_class per component of >= 2 txns, the witness cycles (wit_off,
+        wit_txn, wit_type; empty without witness) and the stats.  The arrays
+        are copies.  max_anti_batches > 0 bounds the G-single test (the bit
+        is then a lower bound: anti_tested < anti_edges)."""
+        a = Anomalies()
+        self._chk(self.lib.hsc_dep_graph_anomalies(self.ctx, ANOM_WITNESS if witness else 0,
+                                                   max_anti_batches, C.byref(a)),
+                  "hsc_dep_graph_anomalies")
+
+        def arr(p, n, dt):
+            if n == 0:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)),
+                                         shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+
+        nc = a.ncomp
+        off = arr(a.wit_off, nc + 1, np.uint32)
+        nw = int(off[-1])
+        out = {"cls": arr(a.cls, a.ntxn, np.uint8), "comp_label": arr(a.comp_label, nc, np.uint32),
+               "comp_class": arr(a.comp_class, nc, np.uint8), "wit_off": off,
+               "wit_txn": arr(a.wit_txn, nw, np.uint32), "wit_type": arr(a.wit_type, nw, np.uint8),
+               "comps": [int(x) for x in a.comps], "txns": [int(x) for x in a.txns]}
+        for k in ("anti_edges", "anti_tested", "core_nodes", "reach_batches", "sweeps", "bfs_levels", "ms"):
+            out[k] = getattr(a, k)
+        return out
 
     def probe_device(self, batch: ProbeBatch) -> None:
         self._chk(self.lib.hsc_probe_device(self.ctx, C.byref(batch)), "hsc_probe_device")

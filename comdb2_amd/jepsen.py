@@ -274,6 +274,61 @@ def g2_illegal(ops: JepsenOps) -> Dict[int, int]:
 
 
 # ---------------------------------------------------------------------------
+# which anomaly, and the transactions to look at
+# ---------------------------------------------------------------------------
+ANOMALY_NAMES = {1: "G1c", 2: "G-single", 4: "G2"}  # hsc_anomalies class bits
+_EDGE_BITS = ((1, "ww"), (2, "wr"), (4, "rw"))
+
+
+def edge_type_name(bits: int) -> str:
+    """"ww" / "wr" / "rw"; an edge merged from several dependencies joins
+    their names with "+" ("wr+rw")."""
+    return "+".join(n for b, n in _EDGE_BITS if bits & b)
+
+
+def anomaly_report(ops: JepsenOps, result: dict) -> dict:
+    """What a reader of a Jepsen result asks of
+    ``Validator.dep_graph_anomalies()``'s dict (a pure function of its
+    arguments): ``valid`` -- no dependency cycle; ``anomaly_types`` -- the
+    sorted classes of the components ("G1c" circular information flow,
+    "G-single" read skew, "G2" an anti-dependency cycle); ``cycles`` -- one
+    entry per component: its ``type``, ``label`` (the component's largest
+    txn), and from the witness its ``txns`` in cycle order, ``edge_types``
+    (the dependency of each step txns[i] -> txns[i + 1], the last one back to
+    txns[0]) and ``ops`` (the txns' completions, ``ops.txn_ops``) -- empty
+    lists when the analysis ran without witnesses; ``g2_keys`` -- adya.clj's
+    own verdict (:func:`g2_illegal`)."""
+    labels = [int(x) for x in result.get("comp_label", ())]
+    classes = [int(x) for x in result.get("comp_class", ())]
+    off = [int(x) for x in result.get("wit_off", ())]
+    wt = [int(x) for x in result.get("wit_txn", ())]
+    wy = [int(x) for x in result.get("wit_type", ())]
+    if len(off) != len(labels) + 1:
+        off = [0] * (len(labels) + 1)
+    cycles = []
+    for i, (lab, k) in enumerate(zip(labels, classes)):
+        txns = wt[off[i]:off[i + 1]]
+        cycles.append({"type": ANOMALY_NAMES[k], "label": lab, "txns": txns,
+                       "edge_types": [edge_type_name(t) for t in wy[off[i]:off[i + 1]]],
+                       "ops": [ops.txn_ops[t] for t in txns]})
+    return {"valid": not labels, "anomaly_types": sorted({c["type"] for c in cycles}),
+            "cycles": cycles, "g2_keys": g2_illegal(ops)}
+
+
+def check_edn(validator, text: str, witness: bool = True) -> dict:
+    """A Jepsen EDN history through the GPU: convert, build the typed graph,
+    classify its cycles; :func:`anomaly_report`'s dict plus ``history`` (the
+    :class:`JepsenOps`) and ``analysis`` (dep_graph_anomalies' dict)."""
+    ops = history_from_jepsen_edn(text)
+    validator.dep_graph_build(ops.history, full=True)
+    result = validator.dep_graph_anomalies(witness=witness)
+    report = anomaly_report(ops, result)
+    report["history"] = ops
+    report["analysis"] = result
+    return report
+
+
+# ---------------------------------------------------------------------------
 # generated histories (test inputs; the reference's clients need a live
 # cluster and a JVM)
 # ---------------------------------------------------------------------------

@@ -717,7 +717,8 @@ int hsc_check_serial(hsc_ctx *ctx, const hsc_serial_msgs *msgs, int *rc_out);
  * writer after the observed version; self edges dropped, parallel edges
  * merged (type bits: 1 ww, 2 wr, 4 rw).  scc_out[v] = the largest txn id of
  * v's strongly connected component; a component with more than one txn is a
- * dependency cycle (G1c / G2 anomaly). */
+ * dependency cycle -- hsc_dep_graph_anomalies (below) tells which anomaly
+ * (G1c / G-single / G2) it is and returns one cycle of it. */
 typedef struct hsc_history {
     size_t nops;
     uint32_t ntxn;
@@ -782,6 +783,56 @@ int hsc_dep_graph_stage_rw_pairs(hsc_ctx *ctx, uint32_t nrs, const uint32_t *rea
 /* scc_out[ntxn] of the last HSC_GRAPH_FULL build (stats as hsc_dep_graph_scc,
  * build_ms 0). */
 int hsc_dep_graph_scc_built(hsc_ctx *ctx, uint32_t *scc_out, hsc_graph_stats *stats);
+/* Which anomaly each dependency cycle of the last HSC_GRAPH_FULL build is
+ * (its edges plus any staged rw pairs, parallel edges merged), and one
+ * witness cycle per component.  E1 = the edges carrying a ww or wr bit
+ * (type & 3); an anti edge has type == 4 exactly.  cls[v] is a mask:
+ *   HSC_ANOM_G1C      v's component of (V, E1) has >= 2 txns (circular
+ *                     information flow);
+ *   HSC_ANOM_GSINGLE  an anti edge a -> b with scc[a] == scc[b] exists such
+ *                     that b reaches v and v reaches a over E1 edges whose ends
+ *                     lie in that component (a cycle with one anti-dependency:
+ *                     read skew);
+ *   HSC_ANOM_G2       v's component has >= 2 txns and holds an anti edge with
+ *                     both ends inside it (write skew at the least).
+ * A txn outside every component of >= 2 txns has cls 0; a component of >= 2
+ * always has a bit (a cycle without an anti edge is an E1 cycle), and its
+ * class comp_class[i] is the lowest bit of the OR of its members' cls.
+ * There is no G0 bit: txn ids are commit order and a key's version order is
+ * its writers' commit order, so every ww edge goes up in txn id and no cycle
+ * is made of ww edges alone.
+ * HSC_ANOM_WITNESS: per component one simple cycle of its class, wit_txn
+ * [wit_off[i], wit_off[i + 1]).  Its closing edge last -> first is the lowest
+ * edge, in the build's (src, dst) order, that is -- class G1c: an E1 edge
+ * whose ends share a component of (V, E1); G-single: an anti edge a -> b with b
+ * reaching a over E1 inside the component; G2: an anti edge inside the
+ * component.  The rest is a shortest path first ~> last, over E1 edges of the
+ * component (G1c, G-single) or all of its edges (G2); which of several
+ * shortest paths is unspecified.
+ * max_anti_batches: the G-single test takes the components' anti edges 64 to
+ * a batch; > 0 stops after that many batches (anti_tested < anti_edges), and
+ * the G-single bit and a component's class are then lower bounds.  0 = all.
+ * The arrays are host memory owned by the context, valid until its next graph
+ * call.  HSC_ESTATE after a raw build, HSC_EDEVICE on a host-only context.
+ * The sharded path (hsc_multi_graph_scc) has no such call: it keeps no typed
+ * edges. */
+#define HSC_ANOM_G1C 1
+#define HSC_ANOM_GSINGLE 2
+#define HSC_ANOM_G2 4
+#define HSC_ANOM_WITNESS 1            /* flags */
+typedef struct hsc_anomalies {
+    uint32_t ntxn;   const uint8_t *cls;          /* [ntxn] */
+    uint32_t ncomp;  const uint32_t *comp_label;  /* [ncomp] ascending; = scc[] label (largest txn) */
+    const uint8_t *comp_class;                    /* [ncomp] lowest bit of the members' OR */
+    const uint32_t *wit_off;                      /* [ncomp+1]; all 0 without HSC_ANOM_WITNESS */
+    const uint32_t *wit_txn;                      /* cycle nodes, starting at the closing edge's dst */
+    const uint8_t  *wit_type;                     /* type bits of edge wit_txn[i] -> next (cyclically) */
+    uint32_t comps[3], txns[3];                   /* components by class / txns carrying each bit */
+    uint64_t anti_edges, anti_tested;             /* anti edges inside components / those tested */
+    uint32_t core_nodes, reach_batches, sweeps, bfs_levels;
+    float ms;                                     /* device time of the analysis, SCC included */
+} hsc_anomalies;
+int hsc_dep_graph_anomalies(hsc_ctx *ctx, unsigned flags, unsigned max_anti_batches, hsc_anomalies *out);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst

@@ -44,6 +44,9 @@ constexpr uint32_t kCTRows = 1u << kCTLog2;  // rows per tile
 // 32.4 vs 32.9 us (r05): a workgroup's time is not its probes in series)
 constexpr int kCLocThreads = 512;
 constexpr int kCLocP = 4;  // probes per locate thread
+// 16-byte pieces of the packed bucket table per locate thread (narrow_trad_buckets: <= 4096 buckets)
+constexpr int kCTradMax = 4096;
+constexpr int kCTradSlots = ((kCTradMax + 1 + 7) / 8 + kCLocThreads - 1) / kCLocThreads;
 constexpr uint32_t kCChunk = kCLocThreads * kCLocP;
 static_assert(kCChunk <= 4096, "in-chunk ranks are 12 bits");
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
@@ -157,8 +160,8 @@ __host__ __device__ inline CLocLds cloc_lds(const CTiles &ct)
     uint32_t o = 0;
     L.first = o;
     o += 8 * ct.WG * ((ct.ntiles + 1) & ~1u);
-    L.trad = o;
-    o += 2 * ((ct.trad_m + 1 + 7) & ~7u);
+    L.trad = o;  // (16-byte aligned: the first keys are an even count of u64)
+    o += (uint32_t)narrow_trad16_bytes(ct.trad_m);
     L.hist = o;
     o += 4 * ((ct.ntiles + 3) & ~3u);
     L.wtot = o;  // the tail's scan: one total per wave
@@ -236,12 +239,27 @@ __global__ __launch_bounds__(kCLocThreads) void k_locate_c(CTiles ct, WinView wt
         }
     }
     {  // first keys, bucket table, histogram into LDS
+        // the packed bucket table's 16-byte pieces are loaded into registers
+        // ahead of the first keys' loop and stored after it (a slot past the
+        // table reads piece 0 again: no branch around a load)
+        const u64x2 *src16 = (const u64x2 *)ct.trad16;
+        const uint32_t np = (uint32_t)(narrow_trad16_bytes(ct.trad_m) / 16);
+        u64x2 st[kCTradSlots];
+#pragma unroll
+        for (int j = 0; j < kCTradSlots; ++j) {
+            const uint32_t i = threadIdx.x + kCLocThreads * j;
+            st[j] = src16[i < np ? i : 0];
+        }
         const uint32_t nf = WG * nt;
         for (uint32_t i = threadIdx.x; i < nf; i += kCLocThreads) lf[i] = ct.first[i];
-        for (uint32_t i = threadIdx.x; i <= ct.trad_m; i += kCLocThreads) T[i] = (uint16_t)ct.trad[i];
         for (uint32_t i = threadIdx.x; i < nt; i += kCLocThreads) hist[i] = 0;
+#pragma unroll
+        for (int j = 0; j < kCTradSlots; ++j) {
+            const uint32_t i = threadIdx.x + kCLocThreads * j;
+            if (i < np) ((u64x2 *)T)[i] = st[j];
+        }
     }
-    const int shift = (int)ct.trad[ct.trad_m + 1];
+    const int shift = ct.trad_shift;
     __syncthreads();
     uint64_t KA[kCLocP][WG], KB[kCLocP][WG], RT[kCLocP];
     uint2 SL[kCLocP];
@@ -541,8 +559,8 @@ __global__ __launch_bounds__(kCJT) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 
 hipError_t ctiles_build(const uint64_t *cw, size_t cs, int WC, const uint32_t *gid,
                         const uint64_t *lsn, const CTiles &ct, uint64_t *key, uint32_t *rank,
-                        uint64_t *first, uint64_t *rel, uint32_t *trad, uint32_t *tb,
-                        hipStream_t s)
+                        uint64_t *first, uint64_t *rel, uint32_t *trad, uint16_t *trad16,
+                        uint32_t *tb, hipStream_t s)
 {
     if (ct.len == 0 || ct.ntiles == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)((ct.len + 255) / 256);
@@ -556,7 +574,7 @@ hipError_t ctiles_build(const uint64_t *cw, size_t cs, int WC, const uint32_t *g
     k_ct_tbuckets<<<ct.ntiles, 256, 0, s>>>(ct, key, tb);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return narrow_trad_build(rel, ct.ntiles, ct.trad_m, trad, s);
+    return narrow_trad_build(rel, ct.ntiles, ct.trad_m, trad, trad16, s);
 }
 
 size_t ctiles_locate_lds(const CTiles &ct) { return cloc_lds(ct).bytes; }
@@ -567,6 +585,7 @@ hipError_t launch_locate_c(const CTiles &ct, const WinView &wt, const ProbeView 
                            uint8_t *flags, hipStream_t s)
 {
     if (p.n == 0 && p.n_lock == 0) return hipSuccess;
+    if (ct.trad_m > (uint32_t)kCTradMax || !ct.trad16) return hipErrorInvalidValue;
     const size_t lds = cloc_lds(ct).bytes;
     const uint32_t blocks = 8 * ((work.G + 7) / 8);
 #define HSC_LOC_C(WG_) \

@@ -578,6 +578,8 @@ struct hsc_ctx {
     // narrow tiles: u32 key deltas + commit ranks (dense batches)
     bool ntiles32 = false;
     DBuf d_trad2;  // the other bucket-table mode (narrow_trad_pick)
+    DBuf d_trad16, d_trad16b;  // packed u16 copies of d_trad / d_trad2 (NarrowTiles::trad16)
+    int trad_shift = 0;        // d_trad[trad_m + 1]: the table's shift (| kTradLog)
     DBuf d_commits, d_cdir, d_tdir, d_trad, d_done, w_vflags, d_key32, d_rank32, d_ctmp[4];
     Dir16 cdir{}, tdir{};
     uint32_t trad_m = 0;       // tile bucket table size (0: none)
@@ -611,7 +613,7 @@ struct hsc_ctx {
     // compact tiles (hsc_ctiles.hip): the compact window as gid || code keys
     bool ctiles = false;
     CTiles ctv{};
-    DBuf d_ckey, d_crank, d_cfirst, d_crel, d_ctrad, d_ctb;
+    DBuf d_ckey, d_crank, d_cfirst, d_crel, d_ctrad, d_ctrad16, d_ctb;
     DBuf d_cph;               // the tiles' point index (PointHash), cph_nb buckets
     uint64_t cph_nb = 0;
     uint32_t cph_ep = 0;      // its epoch (1..2^24-1; 0 = the buffer was never cleared)

@@ -501,16 +501,18 @@ static int build_ctiles(hsc_ctx *c)
     HIPCHK(c, c->d_cfirst.ensure(8 * (size_t)WG * ct.ntiles));
     HIPCHK(c, c->d_crel.ensure(8 * (size_t)ct.ntiles));
     HIPCHK(c, c->d_ctrad.ensure(4 * ((size_t)ct.trad_m + 2)));
+    HIPCHK(c, c->d_ctrad16.ensure(narrow_trad16_bytes(ct.trad_m)));
     HIPCHK(c, c->d_ctb.ensure(4 * (size_t)kTBS * ct.ntiles));
     ct.tb = c->d_ctb.as<uint32_t>();
     ct.key = c->d_ckey.as<uint64_t>();
     ct.rank = c->d_crank.as<uint32_t>();
     ct.first = c->d_cfirst.as<uint64_t>();
     ct.trad = c->d_ctrad.as<uint32_t>();
+    ct.trad16 = c->d_ctrad16.as<uint16_t>();
     HIPCHK(c, ctiles_build(v.words, v.stride, ct.WC, v.gid, v.lsn, ct, c->d_ckey.as<uint64_t>(),
                            c->d_crank.as<uint32_t>(), c->d_cfirst.as<uint64_t>(),
                            c->d_crel.as<uint64_t>(), c->d_ctrad.as<uint32_t>(),
-                           c->d_ctb.as<uint32_t>(), s));
+                           c->d_ctrad16.as<uint16_t>(), c->d_ctb.as<uint32_t>(), s));
     // the point index (hsc_compact.hip PointHash): points are answered by the
     // bound kernel (HSC_PATH_NO_CT_POINTS: they take join records, the r05 path)
     if (!(c->paths & HSC_PATH_NO_CT_POINTS) && ct.n) {
@@ -525,7 +527,11 @@ static int build_ctiles(hsc_ctx *c)
         c->cph_nb = nb;
     }
     HIPCHK(c, hipMemcpyAsync(&ct.base0, c->d_cfirst.p, 8, hipMemcpyDeviceToHost, s));
+    uint32_t shift = 0;  // the bucket table's last entry: a kernel argument of the locate
+    HIPCHK(c, hipMemcpyAsync(&shift, c->d_ctrad.as<uint32_t>() + ct.trad_m + 1, 4,
+                             hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    ct.trad_shift = (int)shift;
     if (getenv("HSC_CT_STATS")) {  // diagnostics: fullest buckets of the locate's and the join's tables
         std::vector<uint32_t> t(ct.trad_m + 2);
         std::vector<uint32_t> tb((size_t)kTBS * ct.ntiles);
@@ -565,8 +571,9 @@ static int narrow_trad_pick(hsc_ctx *c)
         return w;
     };
     const bool log = fullest(b) < fullest(a);
-    if (log) std::swap(c->d_trad, c->d_trad2);
+    if (log) std::swap(c->d_trad, c->d_trad2), std::swap(c->d_trad16, c->d_trad16b);
     c->trad_log = log;
+    c->trad_shift = (int)(log ? b : a)[m + 1];
     return HSC_OK;
 }
 
@@ -943,6 +950,7 @@ static int device_build(hsc_ctx *c, size_t n_in)
     bt.stamp("summaries");
     c->compact = false;
     uint32_t wide32 = 1;   // narrow tiles: a tile spans >= 2^32 codes (device flag)
+    uint32_t trad_shift = 0;  // narrow tiles: the bucket table's shift (tables below 64 buckets)
     bool tiles32 = false;
     c->ctiles = false;
     if (!c->narrow && (c->layout == HSC_LAYOUT_AUTO || c->layout == HSC_LAYOUT_COMPACT_WIDE) &&
@@ -1003,11 +1011,18 @@ static int device_build(hsc_ctx *c, size_t n_in)
             c->trad_m = narrow_trad_buckets(wn.ntiles, c->paths & HSC_PATH_TILE_DIR);
             if (c->trad_m) {
                 HIPCHK(c, c->d_trad.ensure(4 * ((size_t)c->trad_m + 2)));
-                HIPCHK(c, narrow_trad_build(wn.sp_w, wn.ntiles, c->trad_m, c->d_trad.as<uint32_t>(), s));
+                HIPCHK(c, c->d_trad16.ensure(narrow_trad16_bytes(c->trad_m)));
+                HIPCHK(c, narrow_trad_build(wn.sp_w, wn.ntiles, c->trad_m, c->d_trad.as<uint32_t>(),
+                                            c->d_trad16.as<uint16_t>(), s));
                 if (c->trad_m >= 64) {  // the log-mode table too; picked after the build's sync
                     HIPCHK(c, c->d_trad2.ensure(4 * ((size_t)c->trad_m + 2)));
+                    HIPCHK(c, c->d_trad16b.ensure(narrow_trad16_bytes(c->trad_m)));
                     HIPCHK(c, narrow_trad_build(wn.sp_w, wn.ntiles, c->trad_m,
-                                                c->d_trad2.as<uint32_t>(), s, 1));
+                                                c->d_trad2.as<uint32_t>(),
+                                                c->d_trad16b.as<uint16_t>(), s, 1));
+                } else {  // the table's shift (narrow_trad_pick reads it for the larger tables)
+                    HIPCHK(c, hipMemcpyAsync(&trad_shift, c->d_trad.as<uint32_t>() + c->trad_m + 1,
+                                             4, hipMemcpyDeviceToHost, s));
                 }
             }
             HIPCHK(c, c->d_key32.ensure(4 * (size_t)nv.len[0]));
@@ -1024,6 +1039,7 @@ static int device_build(hsc_ctx *c, size_t n_in)
     HIPCHK(c, hipEventRecord(e1, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (tiles32) c->ntiles32 = wide32 == 0;
+    c->trad_shift = (int)trad_shift;
     bt.stamp("tiles");
     if (c->narrow && c->trad_m >= 64) HIPCHK_RC(c, narrow_trad_pick(c));
     float ms = 0;
@@ -1433,6 +1449,7 @@ static void swap_window(hsc_ctx *a, hsc_ctx *b)
     swap(a->d_nsp_w, b->d_nsp_w), swap(a->d_ngs, b->d_ngs), swap(a->d_nscratch, b->d_nscratch);
     swap(a->ntiles32, b->ntiles32), swap(a->d_trad2, b->d_trad2), swap(a->d_commits, b->d_commits);
     swap(a->d_cdir, b->d_cdir), swap(a->d_tdir, b->d_tdir), swap(a->d_trad, b->d_trad);
+    swap(a->d_trad16, b->d_trad16), swap(a->d_trad16b, b->d_trad16b), swap(a->trad_shift, b->trad_shift);
     swap(a->d_key32, b->d_key32), swap(a->d_rank32, b->d_rank32);
     for (int i = 0; i < 4; ++i) swap(a->d_ctmp[i], b->d_ctmp[i]);
     swap(a->cdir, b->cdir), swap(a->tdir, b->tdir), swap(a->trad_m, b->trad_m);
@@ -1454,6 +1471,7 @@ static void swap_window(hsc_ctx *a, hsc_ctx *b)
     swap(a->ctiles, b->ctiles), swap(a->ctv, b->ctv);
     swap(a->d_ckey, b->d_ckey), swap(a->d_crank, b->d_crank), swap(a->d_cfirst, b->d_cfirst);
     swap(a->d_crel, b->d_crel), swap(a->d_ctrad, b->d_ctrad), swap(a->d_ctb, b->d_ctb);
+    swap(a->d_ctrad16, b->d_ctrad16);
     swap(a->d_cph, b->d_cph), swap(a->cph_nb, b->cph_nb), swap(a->cph_ep, b->cph_ep);
 }
 
@@ -2585,6 +2603,8 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
     ntl.tdir = c->tdir;
     ntl.trad = c->trad_m ? c->d_trad.as<uint32_t>() : nullptr;
     ntl.trad_m = c->trad_m;
+    ntl.trad16 = c->trad_m ? c->d_trad16.as<uint16_t>() : nullptr;
+    ntl.trad_shift = c->trad_shift;
     ntl.recs = c->w_trecs.as<uint4>();
     // conflict flags: internal, all zero between batches (the pack clears them)
     const size_t had = c->w_vflags.bytes;
@@ -3343,7 +3363,7 @@ void hsc_ctx_destroy(hsc_ctx *c)
                     &c->w_bucket, &c->w_cursor, &c->w_items, &c->w_item_desc, &c->w_recs,
                     &c->d_nkeys, &c->d_nmaxs, &c->d_nbase, &c->d_nzero, &c->d_ntmax,
                     &c->d_nsp_g, &c->d_nsp_w, &c->d_ngs, &c->d_nscratch, &c->p_code_lo,
-                    &c->p_code_hi, &c->p_zero, &c->d_commits, &c->d_cdir, &c->d_tdir, &c->d_trad, &c->d_done, &c->w_vflags, &c->d_key32, &c->d_rank32,
+                    &c->p_code_hi, &c->p_zero, &c->d_commits, &c->d_cdir, &c->d_tdir, &c->d_trad, &c->d_trad16, &c->d_trad16b, &c->d_done, &c->w_vflags, &c->d_key32, &c->d_rank32,
                     &c->d_ctmp[0], &c->d_ctmp[1], &c->d_ctmp[2], &c->d_ctmp[3], &c->w_tcode,
                     &c->w_tcode2, &c->w_trecs};
     for (DBuf *b : bufs) b->release();

@@ -363,6 +363,10 @@ struct NarrowTiles {
                                // (trad[k] = #first < k << shift; trad[m + 1] = shift),
                                // nullptr: search tdir instead
     uint32_t trad_m;           // buckets (power of two)
+    const uint16_t *trad16;    // trad[0 .. m] packed to u16 (counts <= 4096 tiles), 16-byte
+                               // aligned and zero-padded to whole 16-byte pieces: what the
+                               // locate stages into LDS
+    int trad_shift;            // trad[m + 1], read back by the host after the build
     uint4 *recs;               // chunk areas of 2 x chunk records {lo delta, hi delta, r(S), read set}
 };
 hipError_t check_sorted_u64(const uint64_t *v, size_t n, uint32_t *flag, hipStream_t s);
@@ -382,8 +386,10 @@ uint32_t narrow_tiles_chunk();
 // Bucket table of the tiles' first codes (locate's tile search from LDS);
 // returns the bucket count m (0: too many tiles, use the directory).
 uint32_t narrow_trad_buckets(uint32_t ntiles, bool force_dir = false);
+// trad16: the packed copy (NarrowTiles::trad16), narrow_trad16_bytes(m) bytes
 hipError_t narrow_trad_build(const uint64_t *first, uint32_t ntiles, uint32_t m, uint32_t *trad,
-                             hipStream_t s, int logmode = 0);
+                             uint16_t *trad16, hipStream_t s, int logmode = 0);
+constexpr size_t narrow_trad16_bytes(uint32_t m) { return 2 * (((size_t)m + 1 + 7) & ~(size_t)7); }
 // log-mode bucket of a code (see k_trad): exponent << sv | sv mantissa bits
 constexpr uint32_t kTradLog = 1u << 16;
 __host__ __device__ inline uint32_t trad_log_bucket(uint64_t x, int sv)
@@ -664,7 +670,9 @@ struct CTiles {
     const uint32_t *tb;      // [ntiles][kTBS] per-tile word-0 bucket table (k_ct_tbuckets)
     const uint64_t *first;   // [WG][ntiles] first key of every tile
     const uint32_t *trad;    // [trad_m + 2] bucket table over first word 0 - base0
+    const uint16_t *trad16;  // its packed copy (as NarrowTiles::trad16)
     uint32_t trad_m;
+    int trad_shift;          // trad[trad_m + 1]
     uint64_t base0;          // word 0 of tile 0's first key
     uint64_t rank_base;      // oldest commit LSN of the window
     size_t len;              // row stride (n rounded up to whole tiles)
@@ -694,8 +702,8 @@ uint64_t point_hash_buckets(uint32_t n);
 hipError_t point_hash_build(const CTiles &ct, uint64_t *e, uint64_t nb, uint32_t ep, bool clear, hipStream_t s);
 hipError_t ctiles_build(const uint64_t *cw, size_t cs, int WC, const uint32_t *gid,
                         const uint64_t *lsn, const CTiles &ct, uint64_t *key, uint32_t *rank,
-                        uint64_t *first, uint64_t *rel, uint32_t *trad, uint32_t *tb,
-                        hipStream_t s);
+                        uint64_t *first, uint64_t *rel, uint32_t *trad, uint16_t *trad16,
+                        uint32_t *tb, hipStream_t s);
 size_t ctiles_locate_lds(const CTiles &ct);
 uint32_t ctiles_chunk();
 hipError_t launch_locate_c(const CTiles &ct, const WinView &wt, const ProbeView &p,

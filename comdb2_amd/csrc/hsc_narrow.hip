@@ -1250,6 +1250,39 @@ constexpr int kLocTP = 4;
 constexpr int kLocTThreads = 1024;  // <= 4096 probes per chunk (in-chunk ranks fit 12 bits)
 static_assert(kLocTP * kLocTThreads <= 4096, "in-chunk ranks are 12 bits");
 constexpr int kDirLds = 4400;  // directory entries staged in LDS per directory
+// k_locate_t stages a directory from registers: 16-byte pieces (two entries) per thread
+constexpr int kDirSlots = ((kDirLds + 1) / 2 + kLocTThreads - 1) / kLocTThreads;  // 3
+static_assert((kDirLds + 1) / 2 <= kDirSlots * kLocTThreads, "directory slots of k_locate_t");
+
+// dir16_stage in two halves for a workgroup of THREADS: every load issued
+// into registers (a slot past the directory reads piece 0 again), then,
+// after whatever the caller overlaps with the loads, the LDS stores.  lds_n
+// is a multiple of 16, so a piece never straddles a block; the 17-entry
+// stride leaves the LDS side 8-byte stores.
+template <int THREADS, int SLOTS>
+__device__ __forceinline__ void dir16_stage_issue(const Dir16 &d, u64x2 (&v)[SLOTS])
+{
+    const u64x2 *src = (const u64x2 *)(d.v + d.off[d.lds_from]);
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) {
+        const uint32_t i = threadIdx.x + THREADS * j;
+        v[j] = src[i < d.lds_n / 2 ? i : 0];
+    }
+}
+template <int THREADS, int SLOTS>
+__device__ __forceinline__ void dir16_stage_store(const Dir16 &d, const u64x2 (&v)[SLOTS],
+                                                  uint64_t *lds)
+{
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) {
+        const uint32_t i = threadIdx.x + THREADS * j;
+        if (i < d.lds_n / 2) {
+            uint64_t *o = lds + (i >> 3) * kDirLdsStride + 2 * (i & 7);
+            o[0] = v[j].x;
+            o[1] = v[j].y;
+        }
+    }
+}
 
 template <int W>
 __device__ __forceinline__ void locate_codes(const NarrowView &nv, const ProbeView &p, uint32_t q,
@@ -1290,7 +1323,11 @@ __device__ __forceinline__ void locate_codes(const NarrowView &nv, const ProbeVi
 // for k <= m; trad[m + 1] = shift.
 constexpr uint32_t kTradMaxTiles = 4096;   // first codes staged in LDS (32 KiB)
 constexpr uint32_t kTradMax = 4096;        // buckets (u16 in LDS: 8 KiB)
-
+// k_locate_t stages both from registers: 16-byte pieces per thread
+constexpr int kTradFirstSlots = kTradMaxTiles / 2 / kLocTThreads;  // first codes: 2
+constexpr int kTradSlots = ((kTradMax + 1 + 7) / 8 + kLocTThreads - 1) / kLocTThreads;  // packed table: 1
+static_assert(kTradMaxTiles / 2 <= kTradFirstSlots * kLocTThreads, "first-code slots of k_locate_t");
+static_assert((kTradMax + 1 + 7) / 8 <= kTradSlots * kLocTThreads, "bucket-table slots of k_locate_t");
 uint32_t narrow_trad_buckets(uint32_t ntiles, bool force_dir)
 {
     if (force_dir || ntiles == 0 || ntiles > kTradMaxTiles) return 0;  // force_dir: tests
@@ -1305,10 +1342,17 @@ uint32_t narrow_trad_buckets(uint32_t ntiles, bool force_dir)
 // linear buckets); the build picks the mode whose fullest bucket holds fewer
 // tiles (narrow_trad_pick).
 __global__ void k_trad(const uint64_t *first, uint32_t ntiles, uint32_t m, int logmode,
-                       uint32_t *trad)
+                       uint32_t *trad, uint16_t *trad16)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    // the packed copy's padding (entries m + 1 .. of its last 16-byte piece)
+    if (k > m && k < narrow_trad16_bytes(m) / 2) trad16[k] = 0;
     if (k > m + 1) return;
+    // entry k <= m of both tables (a count of tiles: <= kTradMaxTiles, so it fits u16)
+    auto put = [&](uint32_t v) {
+        trad[k] = v;
+        trad16[k] = (uint16_t)v;
+    };
     const int lg = 31 - __clz(m);
     if (logmode) {
         const int sv = lg - 6;
@@ -1324,7 +1368,7 @@ __global__ void k_trad(const uint64_t *first, uint32_t ntiles, uint32_t m, int l
             else
                 hi = mid;
         }
-        trad[k] = lo;
+        put(lo);
         return;
     }
     const uint64_t span = first[ntiles - 1];
@@ -1335,7 +1379,7 @@ __global__ void k_trad(const uint64_t *first, uint32_t ntiles, uint32_t m, int l
         return;
     }
     if (k == m) {  // every first code is below m << shift (which overflows when span >= 2^63)
-        trad[k] = ntiles;
+        put(ntiles);
         return;
     }
     const uint64_t x = (uint64_t)k << shift;
@@ -1347,14 +1391,18 @@ __global__ void k_trad(const uint64_t *first, uint32_t ntiles, uint32_t m, int l
         else
             hi = mid;
     }
-    trad[k] = lo;
+    put(lo);
 }
 
+static_assert(kTradMaxTiles <= 0xFFFF, "the packed table holds tile counts as u16");
+
 hipError_t narrow_trad_build(const uint64_t *first, uint32_t ntiles, uint32_t m, uint32_t *trad,
-                             hipStream_t s, int logmode)
+                             uint16_t *trad16, hipStream_t s, int logmode)
 {
     if (logmode && m < 64) return hipErrorInvalidValue;
-    k_trad<<<(m + 2 + 255) / 256, 256, 0, s>>>(first, ntiles, m, logmode, trad);
+    if (ntiles > kTradMaxTiles) return hipErrorInvalidValue;
+    // threads 0 .. m + 1 for the u32 table, up to m + 7 for the packed copy's padding
+    k_trad<<<(m + 8 + 255) / 256, 256, 0, s>>>(first, ntiles, m, logmode, trad, trad16);
     return hipGetLastError();
 }
 
@@ -1375,8 +1423,9 @@ __host__ __device__ inline LocLds loc_lds(const NarrowTiles &nt, uint32_t ntiles
     o += nt.rank_lsn32 ? 0 : 8 * dir16_lds_entries(nt.cdir);
     L.hist = o;
     o += 4 * ((ntiles + 3) & ~3u);
+    o = (o + 15) & ~15u;  // (the cdir levels are a multiple of 8 bytes only; the table is stored in 16-byte pieces)
     L.trad = o;
-    o += nt.trad ? 2 * ((nt.trad_m + 1 + 7) & ~7u) : 0;
+    o += nt.trad ? (uint32_t)narrow_trad16_bytes(nt.trad_m) : 0;
     L.sbuf = o;
     o += 8 * kLocTThreads;
     L.rbuf = o;
@@ -1490,19 +1539,50 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
         }
     };
     load(0, 0);
-    int tshift = 0;
+    // Staging: every load is issued here, behind the first sub-chunk's probe
+    // loads, into registers (the slot counts are compile-time, a slot past
+    // the data reads piece 0 again: no branch around a load); the LDS stores
+    // follow the histogram zeroing, so the phase costs one memory round trip
+    // and not one per loop iteration.
+    const int tshift = nt.trad_shift;
+    u64x2 sf[kTradFirstSlots], st[kTradSlots];
+    uint64_t sft = 0;  // an odd tile count's last first code
+    u64x2 sd[kDirSlots], sc[kDirSlots];
     if constexpr (kTrad) {
         const u64x2 *src = (const u64x2 *)wt.sp_w;
-        for (uint32_t i = threadIdx.x; i < ntiles / 2; i += kLocTThreads)
-            ((u64x2 *)tfirst)[i] = src[i];
-        if ((ntiles & 1) && threadIdx.x == 0) tfirst[ntiles - 1] = wt.sp_w[ntiles - 1];
-        for (uint32_t i = threadIdx.x; i <= nt.trad_m; i += kLocTThreads) T[i] = (uint16_t)nt.trad[i];
-        tshift = (int)nt.trad[nt.trad_m + 1];
+        const u64x2 *src16 = (const u64x2 *)nt.trad16;
+#pragma unroll
+        for (int j = 0; j < kTradFirstSlots; ++j) {
+            const uint32_t i = threadIdx.x + kLocTThreads * j;
+            sf[j] = *(i < ntiles / 2 ? src + i : src16);  // (one tile: no whole piece of first codes)
+        }
+        sft = wt.sp_w[ntiles - 1];
+#pragma unroll
+        for (int j = 0; j < kTradSlots; ++j) {
+            const uint32_t i = threadIdx.x + kLocTThreads * j;
+            st[j] = src16[i < narrow_trad16_bytes(nt.trad_m) / 16 ? i : 0];
+        }
     } else {
-        dir16_stage(nt.tdir, tfirst);
+        dir16_stage_issue<kLocTThreads>(nt.tdir, sd);
     }
-    if (!nt.rank_lsn32) dir16_stage(nt.cdir, cdir);
+    if (!nt.rank_lsn32) dir16_stage_issue<kLocTThreads>(nt.cdir, sc);
     for (uint32_t i = threadIdx.x; i < ntiles; i += kLocTThreads) hist[i] = 0;
+    if constexpr (kTrad) {
+#pragma unroll
+        for (int j = 0; j < kTradFirstSlots; ++j) {
+            const uint32_t i = threadIdx.x + kLocTThreads * j;
+            if (i < ntiles / 2) ((u64x2 *)tfirst)[i] = sf[j];
+        }
+        if ((ntiles & 1) && threadIdx.x == 0) tfirst[ntiles - 1] = sft;
+#pragma unroll
+        for (int j = 0; j < kTradSlots; ++j) {
+            const uint32_t i = threadIdx.x + kLocTThreads * j;
+            if (i < narrow_trad16_bytes(nt.trad_m) / 16) ((u64x2 *)T)[i] = st[j];
+        }
+    } else {
+        dir16_stage_store<kLocTThreads>(nt.tdir, sd, tfirst);
+    }
+    if (!nt.rank_lsn32) dir16_stage_store<kLocTThreads>(nt.cdir, sc, cdir);
     __syncthreads();  // directories staged, histogram zeroed
     HSC_STAMP(work, 0, 1);
     const uint64_t *first = kTrad ? tfirst : wt.sp_w;  // first code of every tile
@@ -1720,6 +1800,11 @@ hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeV
     if (p.n == 0 && p.n_lock == 0) return hipSuccess;
     const size_t lds = loc_lds(nt, wt.ntiles).bytes;
     const bool tr = nt.trad != nullptr;
+    // what the kernel's staging slots hold
+    if (tr ? wt.ntiles > kTradMaxTiles || nt.trad_m > kTradMax || !nt.trad16
+           : nt.tdir.lds_n > (uint32_t)kDirLds)
+        return hipErrorInvalidValue;
+    if (!nt.rank_lsn32 && nt.cdir.lds_n > (uint32_t)kDirLds) return hipErrorInvalidValue;
     const int w = nv.W == 1 || nv.W == 2 ? nv.W : 0;
 #define HSC_LOCATE(W_, TR_) \
     k_locate_t<W_, TR_><<<8 * ((work.G + 7) / 8), kLocTThreads, lds, s>>>(nv, wt, p, work, nt, verdict)

@@ -2,9 +2,12 @@
 // and one witness cycle per component, on gfx950.
 //
 // Input: the typed edges of the last full build (GraphBufs src / out_dst /
-// type sorted by (src, dst), type bits 1 ww, 2 wr, 4 rw) and graph_scc's
-// labels.  E1 = the edges carrying a ww or wr bit; an anti edge has type == 4
-// exactly.  Per txn: bit 1 (G1c) its component of (V, E1) has >= 2 txns; bit 2
+// type sorted by (src, dst), type bits 1 ww, 2 wr, 4 rw, 8 rt -- the real-time
+// order of hsc_realtime.hip, present only when it was staged) and graph_scc's
+// labels.  E1 = the edges carrying a ww, wr or rt bit (type & kE1); an anti
+// edge has type == 4 exactly, so an rw edge the real-time order also forces
+// (rw | rt) is E1.  Without rt edges E1 is what it was; with them the three
+// bits below keep their definitions over the widened E1.  Per txn: bit 1 (G1c) its component of (V, E1) has >= 2 txns; bit 2
 // (G-single) an anti edge a -> b of its component closes a cycle b ~> v ~> a
 // over E1 edges of the component; bit 4 (G2) its component holds an anti edge.
 //
@@ -45,6 +48,8 @@ constexpr uint32_t kSelf = 0xFFFFFFFEu;  // parent slot of a BFS source
 // F and B of the batches one launch sweeps together: 64 batches up to 256 K core nodes
 constexpr size_t kReachBytes = 256u << 20;
 constexpr int kSweepsPerSync = 4;
+constexpr uint32_t kE1 = (uint32_t)(kDepWW | kDepWR | kDepRT);
+constexpr uint32_t kAnti = (uint32_t)kDepRW;
 inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
@@ -113,8 +118,8 @@ __global__ void k_an_split_flags(uint32_t me, const uint32_t *ctype, uint32_t *f
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= me) return;
     const uint32_t t = ctype[i];
-    f1[i] = (t & 3u) != 0;
-    fa[i] = t == 4u;
+    f1[i] = (t & kE1) != 0;
+    fa[i] = t == kAnti;
 }
 
 // p1 / pa: the scans of f1 / fa.  E1 rows (src, dst, core edge) and the anti
@@ -126,12 +131,12 @@ __global__ void k_an_split_rows(uint32_t me, const uint32_t *csrc, const uint32_
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= me) return;
     const uint32_t t = ctype[i];
-    if (t & 3u) {
+    if (t & kE1) {
         const uint32_t p = p1[i];
         s1[p] = csrc[i];
         d1[p] = cdst[i];
         e1[p] = i;
-    } else if (t == 4u) {
+    } else if (t == kAnti) {
         const uint32_t p = pa[i];
         aa[p] = csrc[i];
         ab[p] = cdst[i];
@@ -531,7 +536,7 @@ hipError_t graph_anomalies(uint32_t nn, GraphBufs &g, AnomBufs &a, bool witness,
         close[c] = ce;
         wsrc[c] = cdst[ce];
         wtgt[c] = csrc[ce];
-        wmask[c] = k == 4 ? 7u : 3u;  // G1c / G-single paths stay on E1
+        wmask[c] = k == 4 ? (kE1 | kAnti) : kE1;  // G1c / G-single paths stay on E1
     }
     CK(a.wsrc.ensure(4 * (size_t)ncomp));
     CK(a.wtgt.ensure(4 * (size_t)ncomp));

@@ -860,6 +860,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
         if (e != hipSuccess) return e;        \
     } while (0)
     const size_t nops = in.nops;
+    const size_t nx = in.n_extra + in.n_rt;  // staged rows: rw pairs, then the real-time order
     // 1. writers -> unique sorted (key, txn); room for every op (the count
     // comes back with the gather)
     const size_t wcap = std::max<size_t>(64, (nops + 63) & ~(size_t)63);
@@ -924,7 +925,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
         compress_moves(pp.tm, pp.tmv);
         pp.tb = __builtin_popcountll(pp.tm);
     }
-    const bool ww_fused = packed && nops && !full && !in.n_extra;
+    const bool ww_fused = packed && nops && !full && !nx;
     if (ww_fused) {
         const size_t ecap0 = std::max<size_t>(64, ((size_t)nw + 2 * nops + 63) & ~(size_t)63);
         CK(g.ew.ensure(8 * ecap0));
@@ -972,7 +973,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     CK(hipStreamSynchronize(s));
     uint32_t nu = nw ? (uint32_t)meta[0] : 0;
     // 2. edges (capacity for the widest layout: nu + 2 nops + extras)
-    const size_t ne_cap = (size_t)nu + 2 * nops + in.n_extra;
+    const size_t ne_cap = (size_t)nu + 2 * nops + nx;
     const size_t ecap = std::max<size_t>(64, (ne_cap + 63) & ~(size_t)63);
     bool back_listed = false;
     CK(g.ew.ensure(8 * ecap));
@@ -981,8 +982,8 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     CK(g.ew2.ensure(8 * ecap));
     CK(g.et2.ensure(8 * ecap));
     CK(g.eg2.ensure(4 * ecap));
-    uint64_t *et = full || in.n_extra ? g.et.as<uint64_t>() : nullptr;  // raw: rows only
-    uint32_t *eg = full || in.n_extra ? g.eg.as<uint32_t>() : nullptr;
+    uint64_t *et = full || nx ? g.et.as<uint64_t>() : nullptr;  // raw: rows only
+    uint32_t *eg = full || nx ? g.eg.as<uint32_t>() : nullptr;
     if (nu && !(packed && nops)) k_edges_ww<<<blocks(nu), 256, 0, s>>>(nu, wkey, wtxn, g.ew.as<uint64_t>(), et, eg);
     if (nops && packed && nu) {
         // about kPer writers per bucket, at most 2^kDMax buckets.  Config 4
@@ -1016,7 +1017,7 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
         // as the rows are emitted (ww rows are forward: txns ascend inside a
         // key; the counter: g.count's u32 29, cleared by k_graph_meta)
         BackSink sink{nullptr, nullptr, nullptr, 0};
-        if (!full && !in.n_extra && in.ntxn) {
+        if (!full && !nx && in.ntxn) {
             // (HSC_GRAPH_BACK_CAP: a smaller list, read per build -- the
             // tests' way to the diff fallback)
             uint32_t cap = kBackCap;
@@ -1048,19 +1049,24 @@ hipError_t graph_build(const GraphInput &in, GraphBufs &g, bool full, hipStream_
     }
     CK(hipGetLastError());
     const size_t ne_hist = (size_t)nu + 2 * nops;
-    const size_t ne_raw = ne_hist + in.n_extra;
+    const size_t ne_raw = ne_hist + nx;
     if (in.n_extra) {  // staged edges (rw pairs of the validator's join) after the history's
         const size_t o = ne_hist;
         CK(hipMemcpyAsync(g.ew.as<uint64_t>() + o, in.x_rows, 8 * in.n_extra,
                           hipMemcpyDeviceToDevice, s));
         CK(hipMemcpyAsync(g.et.as<uint64_t>() + o, in.x_type, 8 * in.n_extra,
                           hipMemcpyDeviceToDevice, s));
-        CK(hipMemsetAsync(g.eg.as<uint32_t>() + o, 0, 4 * in.n_extra, s));
     }
+    if (in.n_rt) {  // and the staged real-time order after them
+        const size_t o = ne_hist + in.n_extra;
+        CK(hipMemcpyAsync(g.ew.as<uint64_t>() + o, in.r_rows, 8 * in.n_rt, hipMemcpyDeviceToDevice, s));
+        CK(hipMemcpyAsync(g.et.as<uint64_t>() + o, in.r_type, 8 * in.n_rt, hipMemcpyDeviceToDevice, s));
+    }
+    if (nx) CK(hipMemsetAsync(g.eg.as<uint32_t>() + ne_hist, 0, 4 * nx, s));
     g.raw = !full;
     g.ne_raw = ne_raw;
     g.op_cut = !full && txn_sorted;
-    g.op_at = nu, g.op_n = nops, g.x_at = ne_hist, g.x_n = in.n_extra;
+    g.op_at = nu, g.op_n = nops, g.x_at = ne_hist, g.x_n = nx;
     g.back_listed = back_listed;  // graph_cover: the backward rows (count: graph_build_timed)
     g.back_n = 0;
     g.cover_nn = in.ntxn;

@@ -3320,7 +3320,7 @@ int hsc_ctx_create(int device, hsc_ctx **out)
         if (warmed.size() < (size_t)n) warmed.resize(n, false);
         if (!warmed[device]) {
             for (auto f : {warm_kernels, warm_ingest, warm_narrow, warm_ctiles, warm_delta,
-                           warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_anomaly,
+                           warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_realtime, warm_anomaly,
                            warm_route})
                 (void)f();
             warmed[device] = true;
@@ -4548,17 +4548,31 @@ static int graph_build_timed(hsc_ctx *c, const GraphInput &in, bool full, float 
     HIPCHK(c, hipEventCreate(&e1));
     HIPCHK(c, hipEventRecord(e0, s));
     GraphInput gi = in;
-    if (gb.n_extra && c->x_max_txn >= in.ntxn) {  // staged rows would index past the CSR arrays
+    // staged rows that would index past the CSR arrays, or the real-time order
+    // of another history: the build fails and every staged edge is dropped
+    const bool bad_rw = gb.n_extra && c->x_max_txn >= in.ntxn;
+    const bool bad_rt = gb.rt_staged && gb.rt_ntxn != in.ntxn;
+    if (bad_rw || bad_rt) {
         gb.n_extra = 0;
+        gb.rt_staged = false;
+        gb.n_rt = 0;
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
-        return fail(c, HSC_EINVAL, "a staged rw pair names a txn >= the build's ntxn");
+        return fail(c, HSC_EINVAL, bad_rw ? "a staged rw pair names a txn >= the build's ntxn"
+                                          : "the staged real-time order is of another ntxn than the build's");
     }
     if (gb.n_extra) {  // staged edges join this build, once
         gi.x_rows = gb.x_rows.as<uint64_t>();
         gi.x_type = gb.x_type.as<uint64_t>();
         gi.n_extra = gb.n_extra;
         gb.n_extra = 0;
+    }
+    if (gb.rt_staged) {  // and the staged real-time order, a segment of its own
+        gi.r_rows = gb.rt_rows.as<uint64_t>();
+        gi.r_type = gb.rt_type.as<uint64_t>();
+        gi.n_rt = gb.n_rt;
+        gb.rt_staged = false;
+        gb.n_rt = 0;
     }
     gb.edge_bad = nullptr;
     gb.post = nullptr;
@@ -4758,6 +4772,40 @@ int hsc_dep_graph_stage_rw_pairs(hsc_ctx *c, uint32_t nrs, const uint32_t *reads
     HIPCHK(c, hipStreamSynchronize(s));
     if (hb) return fail(c, HSC_EINVAL, "rw pair names a writer LSN or read set not in the map");
     gb.n_extra = n;
+    return HSC_OK;
+}
+
+int hsc_dep_graph_stage_realtime(hsc_ctx *c, uint32_t ntxn, const uint64_t *invoke, const uint64_t *complete,
+                                 uint64_t *n_edges, float *ms)
+{
+    if (!c || (ntxn && (!invoke || !complete))) return HSC_EINVAL;
+    if (c->host_only) return HSC_EDEVICE;
+    MuGuard g(c);
+    (void)hipSetDevice(c->device);
+    GraphBufs &gb = c->graph;
+    gb.rt_staged = false;  // a second call replaces the first; a failed one stages nothing
+    gb.n_rt = 0;
+    if (n_edges) *n_edges = 0;
+    if (ms) *ms = 0;
+    for (uint32_t v = 0; v < ntxn; ++v)
+        if (invoke[v] > complete[v]) return fail(c, HSC_EINVAL, "a txn completes before its invoke");
+    hipStream_t s = c->stream;
+    hipEvent_t e0, e1;
+    HIPCHK(c, hipEventCreate(&e0));
+    HIPCHK(c, hipEventCreate(&e1));
+    hipError_t e = hipEventRecord(e0, s);
+    if (e == hipSuccess) e = realtime_stage(ntxn, invoke, complete, gb, s);
+    const bool too_many = e == hipErrorInvalidValue;
+    if (e == hipSuccess) e = hipEventRecord(e1, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && ms) (void)hipEventElapsedTime(ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (too_many) return fail(c, HSC_EINVAL, "the real-time order has more edges than a build takes");
+    if (e != hipSuccess) gb.n_rt = 0;
+    HIPCHK(c, e);
+    gb.rt_staged = true;
+    if (n_edges) *n_edges = gb.n_rt;
     return HSC_OK;
 }
 

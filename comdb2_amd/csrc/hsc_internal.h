@@ -497,6 +497,7 @@ hipError_t launch_join_t(const ProbeWork &work, const NarrowTiles &nt, uint32_t 
                          uint32_t extra_blocks = 512);
 // Dependency graph + SCC (hsc_graph.hip).
 constexpr uint64_t kDepWW = 1, kDepWR = 2, kDepRW = 4;
+constexpr uint64_t kDepRT = 8;  // real-time order (hsc_realtime.hip): staged only, never from ops
 struct GraphInput {              // device pointers
     const uint32_t *txn;         // [nops] commit order of the op's txn
     const uint64_t *key;
@@ -507,6 +508,9 @@ struct GraphInput {              // device pointers
     // staged extra edges (rows src << 32 | dst, type bits) merged into the build
     const uint64_t *x_rows = nullptr, *x_type = nullptr;
     size_t n_extra = 0;
+    // the staged real-time order (hsc_realtime.hip), a segment of its own after x_rows
+    const uint64_t *r_rows = nullptr, *r_type = nullptr;
+    size_t n_rt = 0;
     bool skip_rw = false;  // reads give wr edges only (rw come from x_rows)
     bool txn_sorted = false;  // ops in nondecreasing txn order (set by the check when it runs)
     bool check = false;       // graph_build checks the ops itself (GraphBufs::bad; an op
@@ -524,6 +528,13 @@ struct GraphBufs {
     DBuf x_rows, x_type, x_map;                // staged extra edges (rw pairs)
     DBuf pk, pdir;                             // packed distinct writers + their directory
     DBuf ptab;                                 // the directory's buckets inline, one line each
+    // staged real-time order (realtime_stage): the sort's rows and their
+    // alternates, suffix minima, per-txn span / count, the edge rows
+    DBuf rt_id, rt_inv, rt_cpl, rt_id2, rt_inv2, rt_cpl2, rt_suf, rt_bmin, rt_span, rt_cnt, rt_sum;
+    DBuf rt_rows, rt_type;
+    size_t n_rt = 0;        // staged real-time edges
+    uint32_t rt_ntxn = 0;   // the txns they were staged for
+    bool rt_staged = false; // an order is staged for the next build (n_rt may be 0)
     size_t n_extra = 0;
     size_t ne = 0;
     size_t ne_raw = 0;  // raw edge slots in ew
@@ -558,7 +569,8 @@ struct GraphBufs {
                        &in_src, &in_dst, &out_off, &in_off, &scc, &active, &color, &mark,
                        &front, &front2, &h_txn, &h_key, &h_isw, &h_obs, &diff, &cut,
                        &cut_id, &txn_of, &x_rows, &x_type, &x_map, &pk, &pdir, &ptab,
-                       &cover_bits, &cover_list, &gvary, &back};
+                       &rt_id, &rt_inv, &rt_cpl, &rt_id2, &rt_inv2, &rt_cpl2, &rt_suf, &rt_bmin,
+                       &rt_span, &rt_cnt, &rt_sum, &rt_rows, &rt_type, &cover_bits, &cover_list, &gvary, &back};
         for (DBuf *b : all) b->release();
     }
 };
@@ -574,6 +586,13 @@ hipError_t graph_pairs_rows(size_t n, const uint32_t *txn, const uint64_t *lsn, 
                             uint32_t *bad, hipStream_t s);
 hipError_t graph_scc(uint32_t nnodes, GraphBufs &g, uint32_t *rounds, uint32_t *iterations,
                      hipStream_t s);
+// The transitive reduction of the real-time order (hsc_realtime.hip): invoke /
+// complete of n txns (host; complete == HSC_RT_OPEN: never completed) -> edge
+// rows a << 32 | b of type kDepRT in g.rt_rows / g.rt_type, g.n_rt of them.
+// More than kRtMaxEdges edges: hipErrorInvalidValue, nothing staged.
+constexpr uint64_t kRtMaxEdges = 0x7FFFFFFFull;
+hipError_t realtime_stage(uint32_t n, const uint64_t *invoke, const uint64_t *complete, GraphBufs &g,
+                          hipStream_t s);
 // Anomaly classes and witness cycles of a full build (hsc_anomaly.hip): the
 // analysis keeps its own buffers, so the build's edges and CSR stay as they
 // are (graph_scc's labels in g.scc are recomputed).
@@ -884,6 +903,7 @@ hipError_t warm_compact();
 hipError_t warm_coalesce();
 hipError_t warm_edges();
 hipError_t warm_graph();
+hipError_t warm_realtime();
 hipError_t warm_anomaly();
 hipError_t warm_route();
 

@@ -190,7 +190,7 @@ EXPORTS = [
     "hsc_collector_check", "hsc_collector_get_stats", "hsc_collector_set_inflight",
     "hsc_set_autocollect",
     "hsc_small_stats", "hsc_harness_concurrent",
-    "hsc_dep_graph_build", "hsc_dep_graph_stage_rw_pairs", "hsc_dep_graph_scc_built", "hsc_dep_graph_build_device", "hsc_dep_graph_cover", "hsc_dep_graph_cut", "hsc_dep_graph_scc_cut",
+    "hsc_dep_graph_build", "hsc_dep_graph_stage_rw_pairs", "hsc_dep_graph_stage_realtime", "hsc_dep_graph_scc_built", "hsc_dep_graph_build_device", "hsc_dep_graph_cover", "hsc_dep_graph_cut", "hsc_dep_graph_scc_cut",
     "hsc_dep_graph_anomalies",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
@@ -203,6 +203,7 @@ EXPORTS = [
     "hsc_multi_set_mode", "hsc_multi_mode", "hsc_multi_routed_phase_stats",
 ]
 MULTI_AUTO, MULTI_PIECES, MULTI_REPLICAS = 0, 1, 2
+RT_OPEN = 0xFFFFFFFFFFFFFFFF  # HSC_RT_OPEN: a txn that never completed (dep_graph_stage_realtime)
 MULTI_ID_BYTES = 2 * 128  # hsc_multi_unique_ids: one RCCL id per lane
 
 (LAYOUT_AUTO, LAYOUT_WIDE, LAYOUT_NARROW, LAYOUT_NARROW_DIRECT, LAYOUT_NARROW_TILES,
@@ -272,6 +273,8 @@ def load() -> C.CDLL:
         "hsc_dep_graph_build": (C.c_int, [_p, C.POINTER(_History), C.c_int, C.POINTER(GraphStats)]),
         "hsc_dep_graph_cover": (C.c_int, [_p, _p]),
         "hsc_dep_graph_stage_rw_pairs": (C.c_int, [_p, C.c_uint32, _p, C.c_size_t, _p, _p]),
+        "hsc_dep_graph_stage_realtime": (C.c_int, [_p, C.c_uint32, _p, _p, C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_float)]),
         "hsc_dep_graph_scc_built": (C.c_int, [_p, _p, C.POINTER(GraphStats)]),
         "hsc_dep_graph_build_device": (C.c_int, [_p, C.c_size_t, C.c_uint32, _p, _p, _p, _p,
                                                  C.c_int, C.POINTER(GraphStats)]),
@@ -1002,6 +1005,22 @@ class Validator:
         self._chk(self.lib.hsc_dep_graph_stage_rw_pairs(self.ctx, len(rt), rt.ctypes.data, len(cl),
                                                         cl.ctypes.data, ct.ctypes.data),
                   "hsc_dep_graph_stage_rw_pairs")
+
+    def dep_graph_stage_realtime(self, invoke, complete) -> dict:
+        """The real-time order (txn a precedes b when complete[a] <
+        invoke[b]; complete == RT_OPEN: never completed) as edges of type 8
+        ("rt") of the next dep_graph_build of len(invoke) txns
+        (hsc_dep_graph_stage_realtime): its transitive reduction, built on
+        the GPU.  Returns ``edges`` (staged) and ``ms`` (device time)."""
+        iv = np.ascontiguousarray(invoke, np.uint64)
+        cp = np.ascontiguousarray(complete, np.uint64)
+        if iv.shape != cp.shape or iv.ndim != 1:
+            raise ValueError("invoke and complete must be 1-d arrays of one length")
+        n, ms = C.c_uint64(), C.c_float()
+        self._chk(self.lib.hsc_dep_graph_stage_realtime(self.ctx, len(iv), iv.ctypes.data, cp.ctypes.data,
+                                                        C.byref(n), C.byref(ms)),
+                  "hsc_dep_graph_stage_realtime")
+        return {"edges": int(n.value), "ms": float(ms.value)}
 
     def dep_graph_scc_built(self, ntxn: int) -> tuple:
         """(scc[ntxn], stats) of the last full build (hsc_dep_graph_scc_built)."""

@@ -120,6 +120,13 @@ class JepsenOps:
     g2_keys: Dict[int, int]  # insert key -> :ok inserts (adya.clj g2-checker input)
     txn_ops: List[dict]      # the completion of each txn (txn id order)
     info_recovered: int = 0  # :info ops whose write a read observed (committed)
+    # each txn's interval in real time (txn id order): an :ok op's is [its
+    # invoke, its completion], a recovered :info op's [its invoke, RT_OPEN]
+    # (it never completed); a completion without an invoke starts at itself.
+    # ``:time`` when every paired op carries an integer one, else line indices
+    # for all ops alike.
+    invoke: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint64))
+    complete: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint64))
 
 
 def _flatten(forms):
@@ -131,7 +138,8 @@ def _flatten(forms):
 
 
 def _pairs(forms):
-    """(ok, info, failed, unpaired): ok / info = [(invoke, completion, line)]."""
+    """(ok, info, failed, unpaired): ok / info = [(invoke, completion, line,
+    the invoke's line or -1)]."""
     pending: Dict[object, Tuple[dict, int]] = {}
     done, infos, failed = [], [], 0
     for i, op in enumerate(_flatten(forms)):
@@ -141,13 +149,13 @@ def _pairs(forms):
         if t == ":invoke":
             pending[p] = (op, i)
         elif t in (":ok", ":fail", ":info"):
-            inv = pending.pop(p, (None, -1))[0]
+            inv, il = pending.pop(p, (None, -1))
             if t == ":fail":
                 failed += 1
             elif t == ":info":
-                infos.append((inv or {}, op, i))
+                infos.append((inv or {}, op, i, il))
             else:
-                done.append((inv or {}, op, i))
+                done.append((inv or {}, op, i, il))
     return done, infos, failed, len(pending)
 
 
@@ -167,8 +175,8 @@ def history_from_jepsen_edn(text: str) -> JepsenOps:
     # every op that may be a txn: (order time, line, invoke, completion, is :ok)
     # -- an :ok op commits at its completion, an :info op (if at all) by its
     # completion, taken as its invoke
-    cands = [(_time(op, i), i, inv, op, True) for inv, op, i in done]
-    cands += [(_time(inv, i) if inv else i, i, inv, op, False) for inv, op, i in infos
+    cands = [(_time(op, i), i, inv, op, True) for inv, op, i, _ in done]
+    cands += [(_time(inv, i) if inv else i, i, inv, op, False) for inv, op, i, _ in infos
               if op.get(":f", inv.get(":f")) in (":write", ":cas")]
     cands.sort(key=lambda c: (c[0], c[1]))
     # per candidate: its ops as (key, is_write, read kind, a, b)
@@ -263,8 +271,29 @@ def history_from_jepsen_edn(text: str) -> JepsenOps:
     h = History(np.array(txn, np.uint32), np.array(key, np.uint64), np.array(isw, np.uint8),
                 np.array(obs, np.int64), len(tid))
     recovered = sum(1 for c in range(len(cands)) if keep[c] and not cands[c][4])
+    invoke, complete = _intervals(done, infos, [cands[c] for c in range(len(cands)) if keep[c]])
     return JepsenOps(h, len(done), failed, len(infos), unpaired, dangling, g2,
-                     [cands[c][3] for c in range(len(cands)) if keep[c]], recovered)
+                     [cands[c][3] for c in range(len(cands)) if keep[c]], recovered, invoke, complete)
+
+
+RT_OPEN = 0xFFFFFFFFFFFFFFFF  # HSC_RT_OPEN: the txn never completed
+
+
+def _intervals(done, infos, kept):
+    """(invoke, complete) of the kept candidates (JepsenOps.invoke / .complete)."""
+    paired = [o for inv, op, _, il in done + infos for o in ((inv, op) if il >= 0 else (op,))]
+    use_time = all(type(o.get(":time")) is int for o in paired)
+    inv_line = {i: il for _, _, i, il in done + infos}  # by the completion's line
+    rows = []
+    for _, i, inv, op, ok in kept:
+        il = inv_line[i]
+        end = op[":time"] if use_time else i
+        start = end if il < 0 else (inv[":time"] if use_time else il)
+        rows.append((min(start, end), end if ok else None))
+    base = min([0] + [r[0] for r in rows])  # (a clock that starts below zero)
+    invoke = np.array([a - base for a, _ in rows], np.uint64)
+    complete = np.array([RT_OPEN if b is None else b - base for _, b in rows], np.uint64)
+    return invoke, complete
 
 
 def g2_illegal(ops: JepsenOps) -> Dict[int, int]:
@@ -277,12 +306,12 @@ def g2_illegal(ops: JepsenOps) -> Dict[int, int]:
 # which anomaly, and the transactions to look at
 # ---------------------------------------------------------------------------
 ANOMALY_NAMES = {1: "G1c", 2: "G-single", 4: "G2"}  # hsc_anomalies class bits
-_EDGE_BITS = ((1, "ww"), (2, "wr"), (4, "rw"))
+_EDGE_BITS = ((1, "ww"), (2, "wr"), (4, "rw"), (8, "rt"))
 
 
 def edge_type_name(bits: int) -> str:
-    """"ww" / "wr" / "rw"; an edge merged from several dependencies joins
-    their names with "+" ("wr+rw")."""
+    """"ww" / "wr" / "rw" / "rt" (the real-time order); an edge merged from
+    several dependencies joins their names with "+" ("wr+rw", "rw+rt")."""
     return "+".join(n for b, n in _EDGE_BITS if bits & b)
 
 
@@ -315,16 +344,46 @@ def anomaly_report(ops: JepsenOps, result: dict) -> dict:
             "cycles": cycles, "g2_keys": g2_illegal(ops)}
 
 
-def check_edn(validator, text: str, witness: bool = True) -> dict:
+def check_edn(validator, text: str, witness: bool = True, realtime: bool = False) -> dict:
     """A Jepsen EDN history through the GPU: convert, build the typed graph,
     classify its cycles; :func:`anomaly_report`'s dict plus ``history`` (the
-    :class:`JepsenOps`) and ``analysis`` (dep_graph_anomalies' dict)."""
+    :class:`JepsenOps`) and ``analysis`` (dep_graph_anomalies' dict).
+
+    ``realtime``: also the strict-serializability (linearizability of whole
+    txns) verdict.  After the plain pass the real-time order of the txns'
+    intervals (``JepsenOps.invoke`` / ``.complete``) is staged as "rt" edges,
+    the graph built and analysed again, and the report gains ``strict_valid``
+    (the second build has no component of >= 2 txns); ``realtime_cycles`` --
+    one entry shaped as those of ``cycles`` per component of the second build
+    none of whose txns has a nonzero ``cls`` in the plain pass, the anomalies
+    that exist only because of real time (each of their cycles takes an rt
+    edge), ``type`` = the class name + "-realtime"; ``realtime_anomaly_types``
+    (their sorted types); ``realtime_analysis`` -- the second analysis dict
+    plus ``edges`` (rt edges staged) and ``stage_ms`` (their device time).
+    ``valid``, ``anomaly_types`` and ``cycles`` keep describing the plain
+    pass."""
     ops = history_from_jepsen_edn(text)
     validator.dep_graph_build(ops.history, full=True)
     result = validator.dep_graph_anomalies(witness=witness)
     report = anomaly_report(ops, result)
     report["history"] = ops
     report["analysis"] = result
+    if not realtime:
+        return report
+    staged = validator.dep_graph_stage_realtime(ops.invoke, ops.complete)
+    validator.dep_graph_build(ops.history, full=True)
+    strict = dict(validator.dep_graph_anomalies(witness=witness))
+    scc, _ = validator.dep_graph_scc_built(ops.history.ntxn)
+    strict["edges"], strict["stage_ms"] = staged["edges"], staged["ms"]
+    plain_cls = np.asarray(result["cls"])
+    cycles = []
+    for c, lab in zip(anomaly_report(ops, strict)["cycles"], strict["comp_label"]):
+        if not plain_cls[np.asarray(scc) == lab].any():
+            cycles.append(dict(c, type=c["type"] + "-realtime"))
+    report["strict_valid"] = len(strict["comp_label"]) == 0
+    report["realtime_cycles"] = cycles
+    report["realtime_anomaly_types"] = sorted({c["type"] for c in cycles})
+    report["realtime_analysis"] = strict
     return report
 
 

@@ -715,7 +715,8 @@ int hsc_check_serial(hsc_ctx *ctx, const hsc_serial_msgs *msgs, int *rc_out);
  * a Jepsen rw-register history with unique write values does.  Edges (Adya):
  * ww consecutive writers of a key, wr writer -> reader, rw reader -> next
  * writer after the observed version; self edges dropped, parallel edges
- * merged (type bits: 1 ww, 2 wr, 4 rw).  scc_out[v] = the largest txn id of
+ * merged (type bits: 1 ww, 2 wr, 4 rw; 8 rt, the real-time order, only when
+ * hsc_dep_graph_stage_realtime staged it).  scc_out[v] = the largest txn id of
  * v's strongly connected component; a component with more than one txn is a
  * dependency cycle -- hsc_dep_graph_anomalies (below) tells which anomaly
  * (G1c / G-single / G2) it is and returns one cycle of it. */
@@ -780,13 +781,41 @@ int hsc_dep_graph_build_device(hsc_ctx *ctx, size_t nops, uint32_t ntxn, const u
 int hsc_dep_graph_stage_rw_pairs(hsc_ctx *ctx, uint32_t nrs, const uint32_t *readset_txn,
                                  size_t ncommit, const uint64_t *commit_lsn,
                                  const uint32_t *commit_txn);
+/* Strict serializability: the real-time order as a fourth edge type.  Txn a
+ * precedes txn b when a completed before b was invoked, complete[a] <
+ * invoke[b] (host arrays of ntxn u64 in the history's txn ids, any monotonic
+ * clock; complete[v] == HSC_RT_OPEN: v never completed -- a recovered :info
+ * op -- and precedes nothing).  The relation is quadratic; what is staged is
+ * its transitive reduction (the pairs not implied by two others: same closure,
+ * so the same components and cycles), at most ntxn x the history's concurrency
+ * edges, as edges of type bit 8 for the next hsc_dep_graph_build /
+ * _build_device of exactly ntxn txns.  They join that build once, merged with
+ * its own edges and any staged rw pairs (type bits OR-ed: wr | rt is a legal
+ * type); a build of another ntxn fails with HSC_EINVAL and drops every staged
+ * edge.  rw pairs and the order may both be staged before one build, in
+ * either order; staging one kind again replaces that kind only.
+ * invoke[v] > complete[v] -> HSC_EINVAL; a host-only context -> HSC_EDEVICE;
+ * ntxn == 0 stages nothing for a build of no txns.  n_edges (may be NULL):
+ * the edges staged; ms (may be NULL): device time of the sort, scan, count
+ * and emit.  hsc_graph_stats counts ww / wr / rw as before (edges includes
+ * every merged edge); hsc_dep_graph_edges returns bit 8 in type like any
+ * other bit.  The sharded path (hsc_multi_graph_scc) takes no real-time
+ * edges. */
+#define HSC_RT_OPEN UINT64_MAX
+int hsc_dep_graph_stage_realtime(hsc_ctx *ctx, uint32_t ntxn, const uint64_t *invoke,
+                                 const uint64_t *complete, uint64_t *n_edges, float *ms);
 /* scc_out[ntxn] of the last HSC_GRAPH_FULL build (stats as hsc_dep_graph_scc,
  * build_ms 0). */
 int hsc_dep_graph_scc_built(hsc_ctx *ctx, uint32_t *scc_out, hsc_graph_stats *stats);
 /* Which anomaly each dependency cycle of the last HSC_GRAPH_FULL build is
- * (its edges plus any staged rw pairs, parallel edges merged), and one
- * witness cycle per component.  E1 = the edges carrying a ww or wr bit
- * (type & 3); an anti edge has type == 4 exactly.  cls[v] is a mask:
+ * (its edges plus any staged rw pairs and real-time order, parallel edges
+ * merged), and one witness cycle per component.  E1 = the edges carrying a
+ * ww, wr or rt bit (type & 11); an anti edge has type == 4 exactly, so an rw
+ * edge that the real-time order also forces (rw | rt) is E1.  Without staged
+ * real-time edges E1 is the ww / wr edges; with them the bits below keep their
+ * definitions over the widened E1 (a read that returns a version overwritten
+ * before the read was invoked is the cycle r -rw-> w -rt-> r: G-single).
+ * cls[v] is a mask:
  *   HSC_ANOM_G1C      v's component of (V, E1) has >= 2 txns (circular
  *                     information flow);
  *   HSC_ANOM_GSINGLE  an anti edge a -> b with scc[a] == scc[b] exists such
@@ -800,7 +829,9 @@ int hsc_dep_graph_scc_built(hsc_ctx *ctx, uint32_t *scc_out, hsc_graph_stats *st
  * class comp_class[i] is the lowest bit of the OR of its members' cls.
  * There is no G0 bit: txn ids are commit order and a key's version order is
  * its writers' commit order, so every ww edge goes up in txn id and no cycle
- * is made of ww edges alone.
+ * is made of ww edges alone; an rt edge between completed txns goes up in
+ * commit order as well (a completed before b was invoked, so before b
+ * completed), so ww and rt edges together make no cycle either.
  * HSC_ANOM_WITNESS: per component one simple cycle of its class, wit_txn
  * [wit_off[i], wit_off[i + 1]).  Its closing edge last -> first is the lowest
  * edge, in the build's (src, dst) order, that is -- class G1c: an E1 edge

@@ -590,6 +590,15 @@ struct hsc_ctx {
     bool rank_lsn32 = false;   // narrow tiles: rows carry lsn - rank_base + 1 (NarrowTiles)
     uint64_t rank_base = 0;
     DBuf w_tcode, w_tcode2, w_trecs;
+    // narrow tiles, the path of a batch (probe_ntiles): without a plan -- the
+    // join scans its tile's column itself -- unless a batch of the last
+    // kHotBatches had a tile of more than kTileCap records, which the kernels
+    // report by storing the batch's number (nt_batch, from 1) into h_hot, a
+    // mapped host word read without synchronising
+    static constexpr uint64_t kHotBatches = 64;
+    HBuf h_hot;
+    uint64_t nt_batch = 0;
+    std::atomic<uint64_t> nt_column{0}, nt_plan{0};  // batches per path (hsc_batch_stats)
     DBuf d_gid, d_words, d_lsn, d_gid2, d_words2, d_lsn2, d_flags, d_scratch;
     DBuf d_pk[2];              // packed-key sort: the keys, ping-pong (hsc_ingest.hip)
     bool packed_sort = false;  // the last build sorted packed keys

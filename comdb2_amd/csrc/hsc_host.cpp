@@ -2611,6 +2611,33 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
     HIPCHK(c, c->w_vflags.ensure((std::max<size_t>(b->n_txn, 1) + 15) & ~(size_t)15));
     if (c->w_vflags.bytes != had) HIPCHK(c, hipMemsetAsync(c->w_vflags.p, 0, c->w_vflags.bytes, s));
     uint8_t *flags = c->w_vflags.as<uint8_t>();
+    // The batch's path.  Balanced window: no plan -- the locate clears the
+    // verdict bytes, the join scans its tiles' columns, runs a tile of more
+    // than kTileCap records in rounds inside its one block and moves the
+    // flags.  The plan and its overflow blocks stay for a skewed window (the
+    // bucket table in log mode) and while a batch of the last kHotBatches had
+    // such a tile: the kernels of either path store the batch's number into
+    // the hot word, which is read here as it stands (a late store only delays
+    // the switch; both paths give the same verdicts).
+    const bool joins = p.n && wn.ntiles;
+    const bool delta = pack_after_delta(c);
+    bool column = false;
+    if (joins) {
+        if (!c->h_hot.p) {
+            if (c->h_hot.ensure(8, true, true)) return fail(c, HSC_ENOMEM, "hot word");
+            *c->h_hot.as<volatile uint64_t>() = 0;
+        }
+        work.hot = (uint64_t *)c->h_hot.dp;
+        work.batch = ++c->nt_batch;
+        const uint64_t hot = *c->h_hot.as<volatile uint64_t>();
+        column = !c->trad_log && !(hot && work.batch - hot <= hsc_ctx::kHotBatches);
+        (column ? c->nt_column : c->nt_plan)++;
+    }
+    if (column) {
+        work.vout = b->verdict;
+        work.n_txn = (uint32_t)b->n_txn;
+        work.bitmap = delta ? nullptr : b->bitmap;
+    }
     const bool tm = c->timing;
     if (tm)
         for (int i = 0; i < 6; ++i)
@@ -2618,12 +2645,19 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
     if (tm) HIPCHK(c, hipEventRecord(c->ev[0], s));
     HIPCHK(c, launch_locate_t(c->nv, wn, p, work, ntl, flags, s));
     if (tm) HIPCHK(c, hipEventRecord(c->ev[1], s));
-    if (p.n && wn.ntiles) {
+    if (column) {
+        // (no plan, no scatter: their legs of the timing are empty)
+        if (tm) HIPCHK(c, hipEventRecord(c->ev[2], s));
+        if (tm) HIPCHK(c, hipEventRecord(c->ev[3], s));
+        HIPCHK(c, launch_join_col(work, ntl, wn.n, wn.ntiles, flags, s));
+        if (tm) HIPCHK(c, hipEventRecord(c->ev[4], s));
+        HIPCHK_RC(c, probe_delta(c, b->verdict));
+        if (delta) HIPCHK(c, launch_pack(b->verdict, (uint32_t)b->n_txn, b->bitmap, s));
+    } else if (joins) {
         // the plan writes the verdict bytes (and bitmap words) from the
         // locate's flags; the join and the delta probe then mark the verdict
         // itself, the join its bitmap bits too (no pack pass unless the delta
         // probe ran: it marks bytes only)
-        const bool delta = pack_after_delta(c);
         work.bitmap = delta ? nullptr : b->bitmap;
         HIPCHK(c, launch_plan_s(work, wn.ntiles, c->w_items.as<uint32_t>(), s, flags,
                                 (uint32_t)b->n_txn, b->verdict));
@@ -3383,6 +3417,7 @@ void hsc_ctx_destroy(hsc_ctx *c)
     for (hipEvent_t &e : c->app_ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     for (HBuf &b : c->h_pend) b.release();
+    c->h_hot.release();
     for (hipEvent_t &e : c->pend_ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     for (DBuf &b : c->co_dev) b.release();
@@ -4439,6 +4474,8 @@ int hsc_batch_stats(hsc_ctx *c, hsc_batch_stats_t *out)
     out->assemble_ns = c->mb_assemble_ns.load();
     out->launch_ns = c->mb_launch_ns.load();
     out->wait_ns = c->mb_wait_ns.load();
+    out->column_batches = c->nt_column.load();
+    out->plan_batches = c->nt_plan.load();
     return HSC_OK;
 }
 

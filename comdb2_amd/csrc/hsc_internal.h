@@ -244,6 +244,18 @@ struct ProbeWork {
     // compact tiles): k_plan_s writes the locate's flags as whole words, the
     // join ORs its hits in (null: verdict bytes only)
     uint64_t *bitmap;
+    // narrow tiles without the plan (k_join_t<true> scans its tile's column
+    // of cm itself): vout = the caller's n_txn verdict bytes, which the locate
+    // zeroes (with the bitmap words) and the join moves the flags into (null:
+    // k_plan_s writes them)
+    uint8_t *vout;
+    uint32_t n_txn;
+    // hot-tile feedback: a tile of more than kTileCap records stores `batch`
+    // (the context's count of narrow-tile batches, from 1) into this word of
+    // mapped host memory, which the host reads when it picks the next batches'
+    // path (null: none)
+    uint64_t *hot;
+    uint64_t batch;
 };
 // Diagnostic phase stamps (HSC_STAMPS builds only): thread 0 of a block
 // records s_memtime at phase boundaries into a buffer of its own (never an
@@ -495,6 +507,12 @@ hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeV
 hipError_t launch_join_t(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,
                          uint32_t ntiles, uint32_t max_items, uint8_t *verdict, hipStream_t s,
                          uint32_t extra_blocks = 512);
+// The join without a plan before it (work.vout set, as for this batch's
+// locate): one block per tile, which scans its tile's column of work.cm, runs
+// every record of the tile (rounds of kJoinChunk) and moves its share of the
+// locate's flags into the verdict bytes (and bitmap), clearing them.
+hipError_t launch_join_col(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,
+                           uint32_t ntiles, uint8_t *flags, hipStream_t s);
 // Dependency graph + SCC (hsc_graph.hip).
 constexpr uint64_t kDepWW = 1, kDepWR = 2, kDepRW = 4;
 constexpr uint64_t kDepRT = 8;  // real-time order (hsc_realtime.hip): staged only, never from ops

@@ -1479,6 +1479,24 @@ struct LocDefer {
     uint64_t snap[K];
 };
 
+// work.vout[0 .. n_txn) and the bitmap's words := 0, workgroup g of work.G
+// (kLocTThreads threads each): 16-byte pieces of the bytes between the
+// buffer's first and last 16-byte boundary, the bytes outside them by
+// workgroup 0's first threads.
+__device__ __forceinline__ void zero_verdicts(const ProbeWork &work, uint32_t g)
+{
+    uint8_t *v = work.vout;
+    const size_t nb = work.n_txn;
+    const size_t head = std::min<size_t>(nb, (16 - ((uintptr_t)v & 15)) & 15);
+    const size_t pieces = (nb - head) / 16, tail = head + 16 * pieces;
+    const size_t t = (size_t)g * kLocTThreads + threadIdx.x, stride = (size_t)work.G * kLocTThreads;
+    for (size_t i = t; i < pieces; i += stride) ((u32x4 *)(v + head))[i] = u32x4{0, 0, 0, 0};
+    if (t < head) v[t] = 0;
+    if (t < nb - tail) v[tail + t] = 0;
+    if (work.bitmap)
+        for (size_t i = t; i < ((size_t)work.n_txn + 63) / 64; i += stride) work.bitmap[i] = 0;
+}
+
 // W = key words held in registers (1 or 2), 0 = read from memory (any W).
 // The chunk's kLocTP probes per thread run as kLocTP sub-chunks of one probe
 // per thread: the loads of sub-chunk s + 1 are in flight while sub-chunk s is
@@ -1786,6 +1804,13 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
                 if (b.x != kNoTile32)
                     area[hist[b.x >> 12] + (b.x & 0xFFFu)] = make_uint4(b.y, b.z, b.w, RT[s][k]);
             }
+        // no plan after this locate: chunk g's workgroup clears its slice of
+        // the caller's verdict bytes and bitmap words (no kernel marks them
+        // before the join).  Issued here, behind the record stores: nothing
+        // in the kernel waits for them (in the prologue the first workgroups'
+        // next probe loads waited for their acknowledgements, +0.9 us on
+        // config 2's one wave of workgroups)
+        if (work.vout) zero_verdicts(work, g);
 #pragma unroll
         for (int k = 0; k < K; ++k)
             if (dfr.x[k] <= dfr.y[k] && dmax[k] > dfr.snap[k]) verdict[RT[S - 1][k]] = 1;
@@ -1827,6 +1852,13 @@ hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeV
 // probes per locate workgroup, directory entries staged in LDS
 uint32_t narrow_tiles_chunk() { return kLocTP * kLocTThreads; }
 uint32_t narrow_tiles_dir_lds() { return kDirLds; }
+
+// A tile of more than kTileCap records tells the host (ProbeWork::hot): every
+// such tile of a batch stores the same value, written through to host memory.
+__device__ __forceinline__ void mark_hot(const ProbeWork &work)
+{
+    if (work.hot) __hip_atomic_store(work.hot, work.batch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // ---- plan ----
 // ctl[1] (extra join items) was zeroed by this batch's locate.
@@ -1909,6 +1941,7 @@ __global__ __launch_bounds__(kPlanSThreads) void k_plan_s(ProbeWork work, uint32
     const uint32_t total = __shfl(x, 63, 64);
     if (lane == 0) work.counts[t] = total;
     if (total > kTileCap) {  // hot tile: join items over its record numbers past kTileCap
+        if (lane == 0) mark_hot(work);
         const uint32_t over = total - kTileCap;
         const uint32_t nx = (over + kJoinChunk - 1) / kJoinChunk;
         uint32_t ib = 0;
@@ -1944,29 +1977,64 @@ hipError_t launch_plan_s(const ProbeWork &work, uint32_t ntiles, uint32_t *ctl, 
 // The tile's column is staged first (its loads ahead of the rows'), each
 // thread finds its records' chunks by a 9-step search of it in LDS and issues
 // the record loads while the rows are still arriving.
-template <bool kTile>
+// kJoinCol (no plan ran): the block reads column `tile` of the locate's
+// chunk-major table itself -- thread g the entry of chunk g, 4-byte loads that
+// the tiles sharing a line of a chunk row (neighbours on one XCD) find in its
+// L2 after the first touch (the table in pieces of 4 tiles, a column 16 bytes
+// apart, measured the same: 41.3 vs 41.5 us per two-stream step, within the
+// spread) -- and scans the counts over its 8 waves: Es, Cs, the tile's total.
+// It runs every record of the tile, kJoinChunk a round; rows, maxima and the
+// column are staged once and only read afterwards.
+enum JoinMode { kJoinItem, kJoinTile, kJoinCol };
+
+// Read set i's flag of the locate into its verdict byte and bitmap bit; set
+// flags are cleared for the next batch.  Only ones are written, so the move
+// commutes with the hits other blocks mark.  Whole waves call it (f = 0 past
+// n_txn): a wave's 64 read sets share one bitmap word.
+__device__ __forceinline__ void move_flag(const ProbeWork &work, uint8_t *flags, uint8_t *verdict,
+                                          uint32_t i, uint8_t f)
+{
+    if (f) verdict[i] = 1, flags[i] = 0;
+    if (work.bitmap) {
+        const uint64_t m = __ballot(f != 0);
+        if (m && (threadIdx.x & 63) == 0) atomicOr((unsigned long long *)&work.bitmap[i >> 6], m);
+    }
+}
+
+template <JoinMode kMode>
 __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowTiles &nt,
                                             uint32_t n, uint32_t xi, uint8_t *verdict,
                                             uint32_t *keys, uint32_t *rank, uint32_t *b16,
-                                            uint32_t *b128, uint32_t *Es, uint32_t *Cs)
+                                            uint32_t *b128, uint32_t *Es, uint32_t *Cs,
+                                            uint32_t rs = 0, uint8_t *flags = nullptr,
+                                            uint32_t *wtot = nullptr)
 {
     constexpr uint32_t T = 1u << kTLog2;
     constexpr int RQ = T / (4 * kJoinThreads);
     constexpr int kRec = kJoinChunk / kJoinThreads;
     static_assert(kMaxChunks <= kJoinThreads, "one column entry per thread");
     uint32_t tile, j0, j1;
-    if constexpr (kTile) {
+    if constexpr (kMode != kJoinItem) {
         tile = xi, j0 = 0;
     } else {
         const uint32_t *d = (const uint32_t *)(work.item_desc + xi);
         tile = sload(d), j0 = sload(d + 1), j1 = sload(d + 2);
     }
     const uint32_t G = work.G;
-    const size_t col = (size_t)tile * hist_stride(G);
     uint32_t e = 0, cs = 0;
-    if (threadIdx.x < G) {
-        e = work.hist[col + threadIdx.x];
-        cs = work.cst[col + threadIdx.x];
+    // this block's share of the flags: the first stride's load goes out ahead
+    // of the column's and the rows'
+    const uint32_t fstride = gridDim.x * kJoinThreads, fi = blockIdx.x * kJoinThreads + threadIdx.x;
+    uint8_t f0 = 0;
+    if constexpr (kMode == kJoinCol) {
+        if (fi < work.n_txn) f0 = flags[fi];
+        if (threadIdx.x < G) e = work.cm[(size_t)threadIdx.x * rs + tile];
+    } else {
+        const size_t col = (size_t)tile * hist_stride(G);
+        if (threadIdx.x < G) {
+            e = work.hist[col + threadIdx.x];
+            cs = work.cst[col + threadIdx.x];
+        }
     }
     u32x4 rk[RQ], rr[RQ], rec[kRec];
     const size_t ts = (size_t)tile << kTLog2;
@@ -1976,23 +2044,63 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
         rk[v] = *(const u32x4 *)(nt.key32 + row);
         rr[v] = *(const u32x4 *)(nt.rank32 + row);
     }
-    if constexpr (kTile) j1 = min(kTileCap, sload(work.counts + tile));
-    if (threadIdx.x < G) Es[threadIdx.x] = e, Cs[threadIdx.x] = cs;
+    if constexpr (kMode == kJoinCol) {
+        move_flag(work, flags, verdict, fi, f0);
+        // (a batch of more read sets than the grid has threads: four loads in flight)
+        for (size_t i = (size_t)fi + fstride; i < work.n_txn; i += 4 * (size_t)fstride) {
+            uint8_t f[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) f[k] = i + (size_t)k * fstride < work.n_txn ? flags[i + (size_t)k * fstride] : 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) move_flag(work, flags, verdict, (uint32_t)(i + (size_t)k * fstride), f[k]);
+        }
+        // block-exclusive scan of the column's counts: wave scans, then the
+        // 8 wave totals through LDS
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const uint32_t cnt = e & 0xFFFFu;
+        uint32_t x = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wtot[wave] = x;
+        __syncthreads();
+        uint32_t run = x - cnt, total = 0;
+#pragma unroll
+        for (int w = 0; w < kJoinThreads / 64; ++w) {
+            const uint32_t t = wtot[w];
+            run += w < wave ? t : 0;
+            total += t;
+        }
+        cs = e >> 16, e = run;
+        j1 = __builtin_amdgcn_readfirstlane(total);
+        if (threadIdx.x == 0) {
+            work.counts[tile] = j1;  // (read back by the timing statistics)
+            if (j1 > kTileCap) mark_hot(work);
+        }
+    }
+    if constexpr (kMode == kJoinTile) j1 = min(kTileCap, sload(work.counts + tile));
+    if (kMode == kJoinCol || threadIdx.x < G) Es[threadIdx.x] = e, Cs[threadIdx.x] = cs;
     __syncthreads();
     HSC_STAMP(work, 1, 1);
     const size_t area = 2 * (size_t)work.chunk;
+    // a round's record loads: records jb .. jb + kJoinChunk of the tile
+    auto fetch = [&](uint32_t jb) {
 #pragma unroll
-    for (int k = 0; k < kRec; ++k) {
-        const uint32_t j = j0 + k * kJoinThreads + threadIdx.x;
-        uint32_t g = 0;  // Es[0] = 0 <= j
+        for (int k = 0; k < kRec; ++k) {
+            const uint32_t j = jb + k * kJoinThreads + threadIdx.x;
+            uint32_t g = 0;  // Es[0] = 0 <= j
 #pragma unroll
-        for (int b = 8; b >= 0; --b) {
-            const uint32_t c = g + (1u << b);
-            if (c < G && Es[c] <= j) g = c;
+            for (int b = 8; b >= 0; --b) {
+                const uint32_t c = g + (1u << b);
+                if (c < G && Es[c] <= j) g = c;
+            }
+            rec[k] = j < j1 ? *(const u32x4 *)(nt.recs + g * area + Cs[g] + (j - Es[g]))
+                            : u32x4{0, 0, 0, 0};
         }
-        rec[k] = j < j1 ? *(const u32x4 *)(nt.recs + g * area + Cs[g] + (j - Es[g]))
-                        : u32x4{0, 0, 0, 0};
-    }
+    };
+    fetch(j0);
 #pragma unroll
     for (int v = 0; v < RQ; ++v) {
         const uint32_t quad = threadIdx.x + kJoinThreads * v;
@@ -2009,30 +2117,39 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
     __syncthreads();
     HSC_STAMP(work, 1, 2);
     const uint32_t tn = min(T, n - (tile << kTLog2));
+    auto walk = [&](uint32_t r0) {
 #pragma unroll
-    for (int k = 0; k < kRec; ++k) {
-        const uint32_t j = j0 + k * kJoinThreads + threadIdx.x;
-        // a wave past the item's records skips the round as a whole; inside,
-        // j < j1 is a predicate (the range maxima are resolved by the wave)
-        if (__builtin_amdgcn_readfirstlane(j) >= j1) continue;
-        const uint32_t lo = rec[k].x, hi = rec[k].y, rs = rec[k].z;
-        uint32_t ja = 1, jb = 1;
+        for (int k = 0; k < kRec; ++k) {
+            const uint32_t j = r0 + k * kJoinThreads + threadIdx.x;
+            // a wave past the item's records skips the round as a whole; inside,
+            // j < j1 is a predicate (the range maxima are resolved by the wave)
+            if (__builtin_amdgcn_readfirstlane(j) >= j1) continue;
+            const uint32_t lo = rec[k].x, hi = rec[k].y, rs = rec[k].z;
+            uint32_t ja = 1, jb = 1;
 #pragma unroll
-        for (int d = 0; d < kTLog2; ++d) {
-            const uint32_t ka = keys[ja], kb = keys[jb];
-            ja = 2 * ja + (ka < lo);
-            jb = 2 * jb + (kb <= hi);
+            for (int d = 0; d < kTLog2; ++d) {
+                const uint32_t ka = keys[ja], kb = keys[jb];
+                ja = 2 * ja + (ka < lo);
+                jb = 2 * jb + (kb <= hi);
+            }
+            const uint32_t kl = keys[0];
+            const uint32_t pa = min(ja - T + (kl < lo), tn);
+            const uint32_t pb = min(jb - T + (kl <= hi), tn);
+            if (wave_any_after32(rank, b16, b128, pa, pb, rs, j < j1 && pa < pb)) {
+                // (r05w, world-1 per-rank step: these atomics 50.7 / 51.9 us per
+                // step, guarded by a read of the verdict byte 53.3 / 52.5, the
+                // pack pass instead 52.7 / 51.9 -- the same within the spread)
+                verdict[rec[k].w] = 1;
+                if (work.bitmap)
+                    atomicOr((unsigned long long *)&work.bitmap[rec[k].w >> 6], 1ull << (rec[k].w & 63));
+            }
         }
-        const uint32_t kl = keys[0];
-        const uint32_t pa = min(ja - T + (kl < lo), tn);
-        const uint32_t pb = min(jb - T + (kl <= hi), tn);
-        if (wave_any_after32(rank, b16, b128, pa, pb, rs, j < j1 && pa < pb)) {
-            // (r05w, world-1 per-rank step: these atomics 50.7 / 51.9 us per
-            // step, guarded by a read of the verdict byte 53.3 / 52.5, the
-            // pack pass instead 52.7 / 51.9 -- the same within the spread)
-            verdict[rec[k].w] = 1;
-            if (work.bitmap)
-                atomicOr((unsigned long long *)&work.bitmap[rec[k].w >> 6], 1ull << (rec[k].w & 63));
+    };
+    walk(j0);
+    if constexpr (kMode == kJoinCol) {  // a hot tile: the rounds past the first
+        for (uint32_t jb = kJoinChunk; jb < j1; jb += kJoinChunk) {
+            fetch(jb);
+            walk(jb);
         }
     }
 }
@@ -2041,8 +2158,12 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
 // 2.09 -> 2.16 G checks/s, join 31.7 -> 29.6 us against tile = block)
 __host__ __device__ inline uint32_t join_tile_blocks(uint32_t ntiles) { return 8 * ((ntiles + 7) / 8); }
 
+// kCol: no plan ran (launch_join_col) -- a block per tile and nothing else;
+// the blocks past the tiles (the grid is a multiple of 8) still move their
+// share of the flags.
+template <bool kCol>
 __global__ __launch_bounds__(kJoinThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_join_t(
-    ProbeWork work, NarrowTiles nt, uint32_t n, uint32_t ntiles, uint8_t *verdict)
+    ProbeWork work, NarrowTiles nt, uint32_t n, uint32_t ntiles, uint8_t *verdict, uint8_t *flags)
 {
     constexpr uint32_t T = 1u << kTLog2;
     __shared__ __attribute__((aligned(16))) uint32_t keys[T];
@@ -2055,15 +2176,26 @@ __global__ __launch_bounds__(kJoinThreads) __attribute__((amdgpu_waves_per_eu(8,
     // chunk-sorted records: neighbouring tiles on one XCD (their runs of a
     // chunk share lines of its record area, which that XCD's L2 then serves)
     const uint32_t tb = join_tile_blocks(ntiles);
-    if (blockIdx.x < tb) {
+    if constexpr (kCol) {
+        __shared__ uint32_t wtot[kJoinThreads / 64];
         const uint32_t tile = xcd_chunk(blockIdx.x, tb / 8);
-        if (tile < ntiles) join_s_item<true>(work, nt, n, tile, verdict, keys, rank, b16, b128, Es, Cs);
+        if (tile < ntiles) {
+            join_s_item<kJoinCol>(work, nt, n, tile, verdict, keys, rank, b16, b128, Es, Cs,
+                                  (ntiles + 3) & ~3u, flags, wtot);
+        } else {
+            for (uint32_t i = blockIdx.x * kJoinThreads + threadIdx.x; i < work.n_txn;
+                 i += gridDim.x * kJoinThreads)
+                move_flag(work, flags, verdict, i, flags[i]);
+        }
+    } else if (blockIdx.x < tb) {
+        const uint32_t tile = xcd_chunk(blockIdx.x, tb / 8);
+        if (tile < ntiles) join_s_item<kJoinTile>(work, nt, n, tile, verdict, keys, rank, b16, b128, Es, Cs);
     } else {  // blocks past the tiles take the hot tiles' overflow items in turn
         const uint32_t nextra = work.item_off[1];
         const uint32_t stride = gridDim.x - tb;
         for (uint32_t xi = blockIdx.x - tb; xi < nextra; xi += stride) {
             __syncthreads();  // the previous item's LDS reads are done
-            join_s_item<false>(work, nt, n, xi, verdict, keys, rank, b16, b128, Es, Cs);
+            join_s_item<kJoinItem>(work, nt, n, xi, verdict, keys, rank, b16, b128, Es, Cs);
         }
     }
     HSC_STAMP(work, 1, 3);
@@ -2078,7 +2210,15 @@ hipError_t launch_join_t(const ProbeWork &work, const NarrowTiles &nt, uint32_t 
     // overflow items (measured: one block per tile beats persistent blocks
     // that prefetch their next tile -- 27.8 vs 32 us on config 2)
     const uint32_t blocks = join_tile_blocks(ntiles) + std::min<uint32_t>(max_items - ntiles, extra_blocks);
-    k_join_t<<<blocks, kJoinThreads, 0, s>>>(work, nt, n, ntiles, verdict);
+    k_join_t<false><<<blocks, kJoinThreads, 0, s>>>(work, nt, n, ntiles, verdict, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_col(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,
+                           uint32_t ntiles, uint8_t *flags, hipStream_t s)
+{
+    if (n == 0 || ntiles == 0 || !work.vout || work.G > (uint32_t)kMaxChunks) return hipErrorInvalidValue;
+    k_join_t<true><<<join_tile_blocks(ntiles), kJoinThreads, 0, s>>>(work, nt, n, ntiles, work.vout, flags);
     return hipGetLastError();
 }
 

@@ -470,10 +470,14 @@ int hsc_small_stats(hsc_ctx *ctx, hsc_small_stats_t *out);
  * walk, dictionary lookups, bound padding), the staging allocation, the SoA
  * assembly; and for the staged path the upload + launch and the wait for a
  * chunk's verdicts (device time + transfers not hidden behind the next
- * chunk's marshal). */
+ * chunk's marshal).  column_batches / plan_batches: dense batches over a
+ * narrow window whose join scanned its tiles' columns itself / that ran the
+ * plan kernel first (a batch with a tile of more than 1024 records sends the
+ * next 64 down the plan path). */
 typedef struct hsc_batch_stats_t {
     uint64_t marshals, read_sets, ranges;
     uint64_t parts_ns, alloc_ns, assemble_ns, launch_ns, wait_ns;
+    uint64_t column_batches, plan_batches;
 } hsc_batch_stats_t;
 int hsc_batch_stats(hsc_ctx *ctx, hsc_batch_stats_t *out);
 

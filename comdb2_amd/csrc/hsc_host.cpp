@@ -3830,6 +3830,9 @@ long hsc_window_export(hsc_ctx *c, int all_versions, uint32_t *gid, uint64_t *ke
     if (copy && !(gid && key_words && lsn)) return HSC_EINVAL;
     MuGuard g(c);
     (void)hipSetDevice(c->device);
+    // a background fold under way holds rows of the snapshot in its frozen run:
+    // wait for it and swap its window in (a failed fold is merged below)
+    if (c->live && c->fn) HIPCHK_RC(c, fold_finish(c, true));
     if (c->live && (c->dn || !c->app_gid.empty())) {  // the snapshot includes the delta run
         c->merge_pending = true;
         c->dirty = true;
@@ -3858,6 +3861,7 @@ int hsc_rw_edges(hsc_ctx *c, const hsc_readsets *rs, size_t *n_pairs, const uint
     if (c->host_only) return HSC_EDEVICE;
     MuGuard g(c);
     (void)hipSetDevice(c->device);
+    if (c->fn) HIPCHK_RC(c, fold_finish(c, true));  // (a frozen run's rows: the fold swaps them in)
     if (c->dn || !c->app_gid.empty()) {  // pairs need every version: fold the delta in first
         c->merge_pending = true;
         c->dirty = true;
@@ -3906,11 +3910,13 @@ int hsc_rw_edges(hsc_ctx *c, const hsc_readsets *rs, size_t *n_pairs, const uint
     const size_t na = c->n_all;
     HIPCHK(c, c->e_flags.ensure(4 * (na + 1) + 64));
     HIPCHK(c, c->e_scratch.ensure(scan_scratch_bytes(na + 1) + 64));
-    HIPCHK(c, c->e_after.ensure((4 + 8 + 8 * (size_t)W) * std::max<size_t>(na, 1)));
     EdgeView w{};
     w.stride = std::max<size_t>(na, 1);
+    // gid [stride] padded to 8 bytes, then lsn [stride] and words [W][stride]
+    const size_t lsn_off = 4 * w.stride + 4 * (w.stride & 1);
+    HIPCHK(c, c->e_after.ensure(lsn_off + (8 + 8 * (size_t)W) * w.stride));
     w.gid = c->e_after.as<uint32_t>();
-    w.lsn = (const uint64_t *)(c->e_after.as<uint8_t>() + 4 * w.stride + 4 * (w.stride & 1));
+    w.lsn = (const uint64_t *)(c->e_after.as<uint8_t>() + lsn_off);
     w.words = w.lsn + w.stride;
     w.W = W;
     uint32_t nafter = 0;

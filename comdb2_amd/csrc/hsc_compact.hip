@@ -167,6 +167,8 @@ __global__ __launch_bounds__(256) void k_compact_probes(ProbeView p, CompactMeta
 }
 
 // ---- exact-key index for point probes (PointHash, hsc_internal.h) ----
+// (ph_mix, ph_key and the home bucket are restated by point_home in
+// tests/compact_placed.py, which places rows by bucket: change them together)
 __device__ __forceinline__ uint64_t ph_mix(uint64_t k0, uint64_t k1, uint64_t k2)
 {
     uint64_t h = k0 * 0x9E3779B97F4A7C15ull;

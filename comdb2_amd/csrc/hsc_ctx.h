@@ -599,6 +599,7 @@ struct hsc_ctx {
     HBuf h_hot;
     uint64_t nt_batch = 0;
     std::atomic<uint64_t> nt_column{0}, nt_plan{0};  // batches per path (hsc_batch_stats)
+    std::atomic<uint64_t> nt_fast{0}, nt_general{0};  // locate launches per instance class
     DBuf d_gid, d_words, d_lsn, d_gid2, d_words2, d_lsn2, d_flags, d_scratch;
     DBuf d_pk[2];              // packed-key sort: the keys, ping-pong (hsc_ingest.hip)
     bool packed_sort = false;  // the last build sorted packed keys

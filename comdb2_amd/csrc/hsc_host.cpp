@@ -2643,7 +2643,9 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
         for (int i = 0; i < 6; ++i)
             if (!c->ev[i]) HIPCHK(c, hipEventCreate(&c->ev[i]));
     if (tm) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    HIPCHK(c, launch_locate_t(c->nv, wn, p, work, ntl, flags, s));
+    int shape = -1;
+    HIPCHK(c, launch_locate_t(c->nv, wn, p, work, ntl, flags, s, &shape));
+    if (shape >= 0) (shape ? c->nt_fast : c->nt_general)++;
     if (tm) HIPCHK(c, hipEventRecord(c->ev[1], s));
     if (column) {
         // (no plan, no scatter: their legs of the timing are empty)
@@ -4482,6 +4484,8 @@ int hsc_batch_stats(hsc_ctx *c, hsc_batch_stats_t *out)
     out->wait_ns = c->mb_wait_ns.load();
     out->column_batches = c->nt_column.load();
     out->plan_batches = c->nt_plan.load();
+    out->fast_locates = c->nt_fast.load();
+    out->general_locates = c->nt_general.load();
     return HSC_OK;
 }
 

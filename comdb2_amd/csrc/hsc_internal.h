@@ -501,9 +501,11 @@ hipError_t launch_plan_s(const ProbeWork &work, uint32_t ntiles, uint32_t *ctl, 
 // Verdict bytes + bitmap from the internal conflict flags; clears the flags.
 hipError_t launch_pack_flags(uint8_t *flags, uint32_t n_txn, uint8_t *verdict, uint64_t *bitmap,
                              hipStream_t s);
+// *shape (unless null): the instance launched -- 1 a fast one (built for the
+// window's shape), 0 the general one, -1 none (an empty batch)
 hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeView &p,
                            const ProbeWork &work, const NarrowTiles &nt, uint8_t *verdict,
-                           hipStream_t s);
+                           hipStream_t s, int *shape = nullptr);
 hipError_t launch_join_t(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,
                          uint32_t ntiles, uint32_t max_items, uint8_t *verdict, hipStream_t s,
                          uint32_t extra_blocks = 512);

@@ -29,6 +29,7 @@
 // of the max tree.  Every group keeps kNP ranges (2 kNP searches) in flight.
 #include "hsc_device.h"
 #include "hsc_internal.h"
+#include "hsc_reldiff.h"
 
 #include <hip/hip_runtime.h>
 
@@ -37,80 +38,8 @@
 namespace hsc {
 
 constexpr uint64_t kKeyPad = ~0ull;      // key padding: above every bound
-constexpr uint64_t kSat = 1ull << 62;    // saturated code: above every key
-
-// (X - B) >> shift for composite keys X = (xg, xw[j * xs]) and B = (bg,
-// bw[j * bs]), limbs most significant first: limb 0 = gid, limb j + 1 = word
-// j.  shift = tz bits of limb lw plus every limb after lw (the window's rows
-// agree on all of those bits).  Returns false if X < B.  Otherwise v =
-// min((X - B) >> shift, sat) and rem = whether the shifted-out bits of X - B
-// are nonzero.
-__host__ __device__ inline bool rel_diff(int W, int lw, int tz, uint64_t xg, const uint64_t *xw,
-                                         size_t xs, uint64_t bg, const uint64_t *bw, size_t bs,
-                                         uint64_t sat, uint64_t &v, bool &rem)
-{
-    uint64_t borrow = 0, d_last = 0, d_prev = 0, high = 0, below = 0;
-    for (int i = W; i >= 0; --i) {
-        const uint64_t x = i ? xw[(size_t)(i - 1) * xs] : xg;
-        const uint64_t b = i ? bw[(size_t)(i - 1) * bs] : bg;
-        const uint64_t d = x - b - borrow;
-        borrow = (x < b) | ((x == b) & (borrow != 0));
-        if (i > lw)
-            below |= d;
-        else if (i == lw)
-            d_last = d;
-        else if (i == lw - 1)
-            d_prev = d;
-        else
-            high |= d;
-    }
-    if (borrow) return false;
-    rem = (below != 0) | (tz ? (d_last & ((1ull << tz) - 1)) != 0 : false);
-    const uint64_t top = tz ? d_prev >> tz : d_prev;
-    const uint64_t low = tz ? (d_last >> tz) | (d_prev << (64 - tz)) : d_last;
-    v = (high | top) ? sat : (low < sat ? low : sat);
-    return true;
-}
-
-// rel_diff for W = 1 or 2 key words held in registers: the words subtract as
-// one 128-bit borrow chain, the gid limb after it; the limb roles come from
-// uniform branches on lw and the shift by tz (< 64) is a funnel shift whose
-// tz = 0 case needs no branch ((d << 1) << 63 = 0).
-template <int W>
-__device__ __forceinline__ bool rel_diff_w(int lw, int tz, uint64_t xg, const uint64_t (&xw)[W],
-                                           uint64_t bg, const uint64_t *bw, uint64_t sat,
-                                           uint64_t &v, bool &rem)
-{
-    static_assert(W == 1 || W == 2, "register form for 1 or 2 words");
-    typedef unsigned __int128 u128;
-    uint64_t d[W + 1];
-    bool borrow;
-    if constexpr (W == 2) {
-        const u128 x = (u128)xw[0] << 64 | xw[1], b = (u128)bw[0] << 64 | bw[1];
-        const u128 dd = x - b;
-        d[1] = (uint64_t)(dd >> 64);
-        d[2] = (uint64_t)dd;
-        borrow = x < b;
-    } else {
-        d[1] = xw[0] - bw[0];
-        borrow = xw[0] < bw[0];
-    }
-    d[0] = xg - bg - (borrow ? 1 : 0);
-    if (xg < bg || (xg == bg && borrow)) return false;
-    uint64_t below, d_last, d_prev, high;
-    if (W == 2 && lw == 2) {
-        below = 0, d_last = d[W], d_prev = d[W - 1], high = d[0];
-    } else if (lw == 1) {
-        below = d[W] & (W == 2 ? ~0ull : 0), d_last = d[1], d_prev = d[0], high = 0;
-    } else {
-        below = d[1] | d[W], d_last = d[0], d_prev = 0, high = 0;
-    }
-    const uint64_t top = d_prev >> tz;
-    const uint64_t low = (d_last >> tz) | ((d_prev << 1) << (63 - tz));
-    rem = (below | (d_last & ((1ull << tz) - 1))) != 0;
-    v = (high | top) ? sat : (low < sat ? low : sat);
-    return true;
-}
+// kSat (the saturated code: above every key), rel_diff, rel_diff_w and the
+// fast instances' rel_short: hsc_reldiff.h
 
 // Compressed codes (nv.comp): code(X) = compress(X over the rows' varying
 // bits) - c0.  Rows map exactly; a bound X that leaves the rows' constant
@@ -1316,6 +1245,36 @@ __device__ __forceinline__ void locate_codes(const NarrowView &nv, const ProbeVi
     hi = live ? v : 0;
 }
 
+// locate_codes of the fast instances (no compressed codes, lw == W): the
+// wave takes the short mapping (hsc_reldiff.h rel_short) when both bounds of
+// every lane meet its precondition -- a lane without a probe counts as
+// meeting it, its codes are never used -- and rel_diff_w otherwise, whole, so
+// the choice is a uniform branch.  bs = the base's limbs, read once.
+template <int W>
+__device__ __forceinline__ void locate_codes_fast(int tz, const uint64_t (&bs)[W + 1], bool valid,
+                                                  uint64_t g, const uint64_t (&xl)[2],
+                                                  const uint64_t (&xh)[2], uint64_t &lo,
+                                                  uint64_t &hi)
+{
+    const uint64_t(&wl)[W] = *(const uint64_t(*)[W])xl;
+    const uint64_t(&wh)[W] = *(const uint64_t(*)[W])xh;
+    const bool fits = !valid || (rel_short_ok<W>(tz, g, wl, bs[0], bs + 1) &&
+                                 rel_short_ok<W>(tz, g, wh, bs[0], bs + 1));
+    uint64_t v = 0, a = 0;
+    bool rem, live;
+    if (__ballot(fits) == ~0ull) {
+        a = rel_short<W>(tz, wl, bs + 1, kSat, v, rem) ? (v >= kSat ? kSat : v + (rem ? 1 : 0)) : 0;
+        live = rel_short<W>(tz, wh, bs + 1, kSat, v, rem);
+    } else {
+        a = rel_diff_w<W>(W, tz, g, wl, bs[0], bs + 1, kSat, v, rem)
+                ? (v >= kSat ? kSat : v + (rem ? 1 : 0))
+                : 0;
+        live = rel_diff_w<W>(W, tz, g, wh, bs[0], bs + 1, kSat, v, rem);
+    }
+    lo = live ? a : kSat;  // a range below the window is empty
+    hi = live ? v : 0;
+}
+
 // ---- bucket table over the tiles' first codes ----
 // first[0] = 0 (codes are relative to the window's first row), so bucket k
 // covers codes [k << shift, (k + 1) << shift) with shift the least that puts
@@ -1408,8 +1367,9 @@ hipError_t narrow_trad_build(const uint64_t *first, uint32_t ntiles, uint32_t m,
 
 // LDS carve of k_locate_t (same on host and device).  Tile bucket mode:
 // first codes [ntiles] + cdir levels + histogram [ntiles] + bucket table u16
-// [m + 1] + per-wave snapshot lists; directory mode: tdir levels instead of
-// the first codes and no bucket table.
+// [m + 1] + per-wave snapshot lists (ranks through the commit directory
+// only); directory mode: tdir levels instead of the first codes and no bucket
+// table.  It depends on nt and ntiles alone, not on the instance launched.
 struct LocLds {
     uint32_t first, cdir, hist, trad, sbuf, rbuf, bytes;
 };
@@ -1426,23 +1386,28 @@ __host__ __device__ inline LocLds loc_lds(const NarrowTiles &nt, uint32_t ntiles
     o = (o + 15) & ~15u;  // (the cdir levels are a multiple of 8 bytes only; the table is stored in 16-byte pieces)
     L.trad = o;
     o += nt.trad ? (uint32_t)narrow_trad16_bytes(nt.trad_m) : 0;
+    // the snapshot lists serve the commit directory only; rbuf's first
+    // kLocTThreads / 64 words hold the waves' totals of the tile scan in
+    // every mode
     L.sbuf = o;
-    o += 8 * kLocTThreads;
+    o += nt.rank_lsn32 ? 0 : 8 * kLocTThreads;
     L.rbuf = o;
-    o += 4 * kLocTThreads;
+    o += 4 * (nt.rank_lsn32 ? kLocTThreads / 64 : kLocTThreads);
     L.bytes = o;
     return L;
 }
 
 // #first < x[k] over the LDS bucket table: bucket, then a binary search
 // inside it (typically 0-1 steps; a crowded bucket costs log2 of its size).
-template <int K>
+// kMode: the table's mode when the instance fixes it (0 linear, 1 log), -1 =
+// read from shift.
+template <int K, int kMode = -1>
 __device__ __forceinline__ void trad_count(const uint64_t *first, const uint16_t *T, uint32_t m,
                                            int shift, uint32_t ntiles, const uint64_t (&x)[K],
                                            const bool (&act)[K], uint32_t (&out)[K])
 {
     uint32_t l[K], h[K];
-    const bool lg = (shift & kTradLog) != 0;
+    const bool lg = kMode < 0 ? (shift & kTradLog) != 0 : kMode == 1;
     const int sv = shift & 0xFFFF;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -1503,11 +1468,23 @@ __device__ __forceinline__ void zero_verdicts(const ProbeWork &work, uint32_t g)
 // located (codes, snapshot ranks, end tiles, records), so the chunk's HBM
 // reads overlap its LDS / VALU work instead of preceding it.  (r02,
 // chunk-sorted records: 1 probe per sub-chunk 2.10 G vs 2 probes 2.00 G.)
-template <int W, bool kTrad>
+//
+// kShape: what the launch knows of the window and fixes for the instance.
+// kLocGeneral reads everything from nv / nt at run time.  The fast shapes
+// (kLocFastLin, kLocFastLog: W = 1 or 2 with the bucket table in linear / log
+// mode) hold for a window without compressed codes whose last key word is its
+// last varying limb (lw == W), with ranks in lsn32 mode, and a batch with
+// probes (p.n > 0): no commit directory (its staging slots, snapshot lists
+// and head search are not compiled), the bucket form a constant, bounds
+// through locate_codes_fast.
+constexpr int kLocGeneral = 0, kLocFastLin = 1, kLocFastLog = 2;
+template <int W, bool kTrad, int kShape = kLocGeneral>
 __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinView wt, ProbeView p,
                                                            ProbeWork work, NarrowTiles nt,
                                                            uint8_t *verdict)
 {
+    constexpr bool kFast = kShape != kLocGeneral;
+    static_assert(!kFast || (kTrad && (W == 1 || W == 2)), "fast shapes: bucket table, 1 or 2 words");
     constexpr int WR = 2 > W ? 2 : W;
     constexpr int K = 1, S = kLocTP;  // probes per sub-chunk and thread, sub-chunks
     extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
@@ -1546,13 +1523,16 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
             const uint32_t q = valid[buf][k] ? qq[buf][k] : 0;
             // read-once inputs: non-temporal, so they do not push the window's
             // rows out of the caches between batches
-            gg[buf][k] = p.n ? __builtin_nontemporal_load(p.gid + q) : 0;
-            snap[buf][k] = p.n ? __builtin_nontemporal_load(p.snap + q) : 0;
-            tx[buf][k] = p.n ? __builtin_nontemporal_load(p.txn + q) : 0;
+            // (a batch of table locks only has no probe arrays; the fast
+            // shapes are launched with probes)
+            const bool some = kFast || p.n;
+            gg[buf][k] = some ? __builtin_nontemporal_load(p.gid + q) : 0;
+            snap[buf][k] = some ? __builtin_nontemporal_load(p.snap + q) : 0;
+            tx[buf][k] = some ? __builtin_nontemporal_load(p.txn + q) : 0;
 #pragma unroll
             for (int w = 0; w < W; ++w) {
-                xl[buf][k][w] = p.n ? __builtin_nontemporal_load(p.lo + (size_t)w * p.n + q) : 0;
-                xh[buf][k][w] = p.n ? __builtin_nontemporal_load(p.hi + (size_t)w * p.n + q) : 0;
+                xl[buf][k][w] = some ? __builtin_nontemporal_load(p.lo + (size_t)w * p.n + q) : 0;
+                xh[buf][k][w] = some ? __builtin_nontemporal_load(p.hi + (size_t)w * p.n + q) : 0;
             }
         }
     };
@@ -1583,7 +1563,8 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
     } else {
         dir16_stage_issue<kLocTThreads>(nt.tdir, sd);
     }
-    if (!nt.rank_lsn32) dir16_stage_issue<kLocTThreads>(nt.cdir, sc);
+    const bool lsn32 = kFast || nt.rank_lsn32;
+    if (!lsn32) dir16_stage_issue<kLocTThreads>(nt.cdir, sc);
     for (uint32_t i = threadIdx.x; i < ntiles; i += kLocTThreads) hist[i] = 0;
     if constexpr (kTrad) {
 #pragma unroll
@@ -1600,10 +1581,17 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
     } else {
         dir16_stage_store<kLocTThreads>(nt.tdir, sd, tfirst);
     }
-    if (!nt.rank_lsn32) dir16_stage_store<kLocTThreads>(nt.cdir, sc, cdir);
+    if (!lsn32) dir16_stage_store<kLocTThreads>(nt.cdir, sc, cdir);
     __syncthreads();  // directories staged, histogram zeroed
     HSC_STAMP(work, 0, 1);
     const uint64_t *first = kTrad ? tfirst : wt.sp_w;  // first code of every tile
+    // the fast shapes' base limbs and shift (uniform: scalar loads, once)
+    uint64_t fbase[kFast ? W + 1 : 1] = {};
+    const int ftz = nv.tz;
+    if constexpr (kFast) {
+#pragma unroll
+        for (int i = 0; i <= W; ++i) fbase[i] = nv.base[i];
+    }
     LocDefer<K> dfr;
 #pragma unroll
     for (int k = 0; k < K; ++k) dfr.x[k] = 1, dfr.y[k] = 0;
@@ -1627,15 +1615,20 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
         // 3. locate this sub-chunk from registers and LDS
         uint64_t lo[K], hi[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k)
-            locate_codes<W>(nv, p, valid[cb][k] ? qq[cb][k] : 0, gg[cb][k], xl[cb][k], xh[cb][k],
-                            lo[k], hi[k]);
+        for (int k = 0; k < K; ++k) {
+            if constexpr (kFast)
+                locate_codes_fast<W>(ftz, fbase, valid[cb][k], gg[cb][k], xl[cb][k], xh[cb][k],
+                                     lo[k], hi[k]);
+            else
+                locate_codes<W>(nv, p, valid[cb][k] ? qq[cb][k] : 0, gg[cb][k], xl[cb][k],
+                                xh[cb][k], lo[k], hi[k]);
+        }
         // Snapshot ranks r(S): O(1) when the window spans < 2^32 of log, else
         // #commits <= S through the commit directory; a run of equal
         // snapshots in neighbouring lanes (a read set's ranges) has one head,
         // the wave packs its heads into a list and searches each once.
         uint32_t rs[K];
-        if (nt.rank_lsn32) {
+        if (lsn32) {
 #pragma unroll
             for (int k = 0; k < K; ++k) rs[k] = lsn32_rank(snap[cb][k], nt.rank_base);
         } else {
@@ -1657,7 +1650,8 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
                 act[2 * k] = act[2 * k + 1] = valid[cb][k] && lo[k] <= hi[k];
             }
             if constexpr (kTrad)
-                trad_count<2 * K>(tfirst, T, nt.trad_m, tshift, ntiles, keys, act, cnt);
+                trad_count<2 * K, kFast ? kShape == kLocFastLog : -1>(tfirst, T, nt.trad_m, tshift,
+                                                                      ntiles, keys, act, cnt);
             else
                 dir16_count<2 * K>(nt.tdir, tfirst, keys, act, cnt);
         }
@@ -1711,7 +1705,7 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
 #pragma unroll
     for (int k = 0; k < K; ++k) dmax[k] = dfr.x[k] <= dfr.y[k] ? tiles_max(wt, dfr.x[k], dfr.y[k]) : 0;
     {
-        if (!nt.rank_lsn32) {  // the chunk's snapshot ranks: heads of all sub-chunks in one list
+        if (!lsn32) {  // the chunk's snapshot ranks: heads of all sub-chunks in one list
             const uint64_t le_mask = lane == 63 ? ~0ull : ((2ull << lane) - 1);
             bool head[S][K];
             uint32_t slot[S][K];
@@ -1820,8 +1814,9 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
 
 hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeView &p,
                            const ProbeWork &work, const NarrowTiles &nt, uint8_t *verdict,
-                           hipStream_t s)
+                           hipStream_t s, int *shape)
 {
+    if (shape) *shape = -1;
     if (p.n == 0 && p.n_lock == 0) return hipSuccess;
     const size_t lds = loc_lds(nt, wt.ntiles).bytes;
     const bool tr = nt.trad != nullptr;
@@ -1831,9 +1826,24 @@ hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeV
         return hipErrorInvalidValue;
     if (!nt.rank_lsn32 && nt.cdir.lds_n > (uint32_t)kDirLds) return hipErrorInvalidValue;
     const int w = nv.W == 1 || nv.W == 2 ? nv.W : 0;
-#define HSC_LOCATE(W_, TR_) \
-    k_locate_t<W_, TR_><<<8 * ((work.G + 7) / 8), kLocTThreads, lds, s>>>(nv, wt, p, work, nt, verdict)
-    if (w == 1 && tr)
+    // the window's shape: the fast instances are built for a batch with
+    // probes over a bucket-table window of 1 or 2 words, no compressed codes,
+    // the last word the last varying limb, ranks in lsn32 mode (W = 1 with a
+    // log table has no instance: it takes the general one)
+    const bool log = tr && (nt.trad_shift & (int)kTradLog) != 0;
+    const bool fast = tr && w != 0 && !nv.comp && nv.lw == nv.W && nt.rank_lsn32 && p.n > 0 &&
+                      !(log && w == 1);
+    if (shape) *shape = fast ? 1 : 0;
+#define HSC_LOCATE(W_, TR_, ...)                                                                  \
+    k_locate_t<W_, TR_, ##__VA_ARGS__><<<8 * ((work.G + 7) / 8), kLocTThreads, lds, s>>>(nv, wt, p, work, \
+                                                                                   nt, verdict)
+    if (fast && w == 1)
+        HSC_LOCATE(1, true, kLocFastLin);
+    else if (fast && !log)
+        HSC_LOCATE(2, true, kLocFastLin);
+    else if (fast)
+        HSC_LOCATE(2, true, kLocFastLog);
+    else if (w == 1 && tr)
         HSC_LOCATE(1, true);
     else if (w == 1)
         HSC_LOCATE(1, false);

@@ -473,11 +473,15 @@ int hsc_small_stats(hsc_ctx *ctx, hsc_small_stats_t *out);
  * chunk's marshal).  column_batches / plan_batches: dense batches over a
  * narrow window whose join scanned its tiles' columns itself / that ran the
  * plan kernel first (a batch with a tile of more than 1024 records sends the
- * next 64 down the plan path). */
+ * next 64 down the plan path).  fast_locates / general_locates: launches of
+ * the narrow-tile locate by instance -- one built for the window's shape (1
+ * or 2 key words, the last one varying, bucket table, no compressed codes,
+ * 32-bit commit ranks) / the one that reads the shape at run time. */
 typedef struct hsc_batch_stats_t {
     uint64_t marshals, read_sets, ranges;
     uint64_t parts_ns, alloc_ns, assemble_ns, launch_ns, wait_ns;
     uint64_t column_batches, plan_batches;
+    uint64_t fast_locates, general_locates;
 } hsc_batch_stats_t;
 int hsc_batch_stats(hsc_ctx *ctx, hsc_batch_stats_t *out);
 

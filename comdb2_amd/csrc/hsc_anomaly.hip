@@ -12,9 +12,10 @@
 // over E1 edges of the component; bit 4 (G2) its component holds an anti edge.
 //
 // Steps:
-//   core     the txns of nontrivial components relabelled densely (txn order)
-//            and the edges inside a component: a flag + scan compaction over
-//            the nodes and over the edges; everything after it costs O(core)
+//   core     (graph_core, which hsc_si.hip calls as well) the txns of
+//            nontrivial components relabelled densely (txn order) and the
+//            edges inside a component: a flag + scan compaction over the nodes
+//            and over the edges; everything after it costs O(core)
 //   G1c      graph_scc of the core restricted to E1 (its own GraphBufs; the
 //            CSC by counting, the colouring does not need sorted rows)
 //   G-single bit-parallel reach: the core's anti edges in (src, dst) order, 64
@@ -304,18 +305,28 @@ __global__ void k_an_bfs_step(const uint32_t *front, uint32_t nf, const uint32_t
     }
 }
 
-void AnomBufs::release_all()
+void CoreBufs::release_core()
 {
     DBuf *all[] = {&flag, &id, &node_txn, &root, &cid, &comp_of, &comp_label, &eflag, &epos, &csrc,
-                   &cdst, &ctype, &coff, &f1, &fa, &s1, &e1i, &aa, &ab, &ae, &closed, &F, &B, &gs,
-                   &g1c, &cg2, &cls, &wmin, &wsrc, &wtgt, &wmask, &pedge, &target, &front, &front2,
-                   &scratch, &cnt};
+                   &cdst, &ctype, &coff, &f1, &fa, &s1, &e1i, &aa, &ab, &ae, &scratch};
     for (DBuf *b : all) b->release();
     e1.release_all();
 }
 
-hipError_t graph_anomalies(uint32_t nn, GraphBufs &g, AnomBufs &a, bool witness, uint32_t max_batches,
-                           AnomOut &out, hipStream_t s)
+void AnomBufs::release_all()
+{
+    DBuf *all[] = {&closed, &F, &B, &gs, &g1c, &cg2, &cls, &wmin, &wsrc, &wtgt, &wmask, &pedge,
+                   &target, &front, &front2, &cnt};
+    for (DBuf *b : all) b->release();
+    release_core();
+}
+
+// graph_scc of the build, then step "core" of the header comment: the dense
+// relabelling, the typed CSR of the edges inside a component, the E1 / anti
+// split (f1 / fa hold their exclusive scans afterwards) and the CSR / CSC of
+// (core, E1) in a.e1.  d.nc == 0: no component of >= 2 txns, nothing else set.
+hipError_t graph_core(uint32_t nn, GraphBufs &g, CoreBufs &a, CoreDims &d, uint32_t *rounds,
+                      uint32_t *iterations, hipStream_t s)
 {
     hipError_t e = hipSuccess;
 #define CK(x)                                 \
@@ -323,11 +334,9 @@ hipError_t graph_anomalies(uint32_t nn, GraphBufs &g, AnomBufs &a, bool witness,
         e = (x);                              \
         if (e != hipSuccess) return e;        \
     } while (0)
-    out.clear(nn);
-    if (nn == 0) return hipSuccess;
-    CK(graph_scc(nn, g, &out.scc_rounds, &out.scc_iterations, s));
+    d = CoreDims{0, 0, 0, 0, 0};
+    CK(graph_scc(nn, g, rounds, iterations, s));
     const uint32_t *scc = g.scc.as<uint32_t>();
-
     // ---- a. core: nodes ----
     CK(a.flag.ensure(4 * ((size_t)nn + 1)));
     CK(a.id.ensure(4 * ((size_t)nn + 1)));
@@ -339,7 +348,7 @@ hipError_t graph_anomalies(uint32_t nn, GraphBufs &g, AnomBufs &a, bool witness,
     uint32_t nc = 0;
     CK(hipMemcpyAsync(&nc, a.id.as<uint32_t>() + nn, 4, hipMemcpyDeviceToHost, s));
     CK(hipStreamSynchronize(s));
-    out.core_nodes = nc;
+    d.nc = nc;
     if (nc == 0) return hipSuccess;
     CK(a.node_txn.ensure(4 * (size_t)nc));
     CK(a.root.ensure(4 * ((size_t)nc + 1)));
@@ -415,6 +424,32 @@ hipError_t graph_anomalies(uint32_t nn, GraphBufs &g, AnomBufs &a, bool witness,
     CK(hipMemcpyAsync(g1.flags.p, g1.in_off.p, 4 * ((size_t)nc + 1), hipMemcpyDeviceToDevice, s));
     if (m1) k_an_infill<<<blocks(m1), 256, 0, s>>>(m1, s1, d1, g1.flags.as<uint32_t>(), g1.in_src.as<uint32_t>());
     CK(hipGetLastError());
+    d.ncomp = ncomp;
+    d.me = me;
+    d.m1 = m1;
+    d.na = na;
+#undef CK
+    return hipSuccess;
+}
+
+hipError_t graph_anomalies(uint32_t nn, GraphBufs &g, AnomBufs &a, bool witness, uint32_t max_batches,
+                           AnomOut &out, hipStream_t s)
+{
+    hipError_t e = hipSuccess;
+#define CK(x)                                 \
+    do {                                      \
+        e = (x);                              \
+        if (e != hipSuccess) return e;        \
+    } while (0)
+    out.clear(nn);
+    if (nn == 0) return hipSuccess;
+    CoreDims cd;
+    CK(graph_core(nn, g, a, cd, &out.scc_rounds, &out.scc_iterations, s));
+    const uint32_t nc = cd.nc, ncomp = cd.ncomp, me = cd.me, m1 = cd.m1, na = cd.na;
+    out.core_nodes = nc;
+    if (nc == 0) return hipSuccess;
+    GraphBufs &g1 = a.e1;
+    uint32_t *s1 = a.s1.as<uint32_t>(), *d1 = g1.out_dst.as<uint32_t>();
 
     // ---- b. G1c: the components of (core, E1) ----
     uint32_t r1 = 0, i1 = 0;
@@ -595,6 +630,12 @@ hipError_t graph_anomalies(uint32_t nn, GraphBufs &g, AnomBufs &a, bool witness,
     }
 #undef CK
     return hipSuccess;
+}
+
+hipError_t scc_members(uint32_t n, const uint32_t *label, uint32_t *flag, hipStream_t s)
+{
+    if (n) k_an_member<<<blocks(n), 256, 0, s>>>(n, label, flag);
+    return hipGetLastError();
 }
 
 // load this file's code object now (see warm_graph)

@@ -675,6 +675,8 @@ struct hsc_ctx {
     uint32_t x_max_txn = 0;  // largest txn id a staged rw pair can name (stage_rw_pairs)
     AnomBufs anom;           // hsc_dep_graph_anomalies: device scratch, host results
     AnomOut anom_out;
+    SiBufs si;               // hsc_dep_graph_si: device scratch, host results
+    SiOut si_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

@@ -3356,7 +3356,7 @@ int hsc_ctx_create(int device, hsc_ctx **out)
         if (warmed.size() < (size_t)n) warmed.resize(n, false);
         if (!warmed[device]) {
             for (auto f : {warm_kernels, warm_ingest, warm_narrow, warm_ctiles, warm_delta,
-                           warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_realtime, warm_anomaly,
+                           warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_realtime, warm_anomaly, warm_si,
                            warm_route})
                 (void)f();
             warmed[device] = true;
@@ -3432,6 +3432,7 @@ void hsc_ctx_destroy(hsc_ctx *c)
     }
     c->graph.release_all();
     c->anom.release_all();
+    c->si.release_all();
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -4934,6 +4935,59 @@ int hsc_dep_graph_anomalies(hsc_ctx *c, unsigned flags, unsigned max_anti_batche
     out->core_nodes = o.core_nodes;
     out->reach_batches = o.reach_batches;
     out->sweeps = (uint32_t)std::min<uint64_t>(o.sweeps, 0xFFFFFFFFull);
+    out->bfs_levels = o.bfs_levels;
+    return HSC_OK;
+}
+
+int hsc_dep_graph_si(hsc_ctx *c, unsigned flags, hsc_si_report *out)
+{
+    if (!c || !out) return HSC_EINVAL;
+    if (c->host_only) return HSC_EDEVICE;
+    MuGuard g(c);
+    (void)hipSetDevice(c->device);
+    GraphBufs &gb = c->graph;
+    const uint32_t nn = c->graph_ntxn;
+    if (gb.raw) return fail(c, HSC_ESTATE, "last build kept raw rows only (no HSC_GRAPH_FULL)");
+    hipStream_t s = c->stream;
+    hipEvent_t e1, e2;
+    HIPCHK(c, hipEventCreate(&e1));
+    HIPCHK(c, hipEventCreate(&e2));
+    HIPCHK(c, hipEventRecord(e1, s));
+    SiOut &o = c->si_out;
+    hipError_t e = graph_si(nn, gb, c->si, (flags & HSC_SI_WITNESS) != 0, o, s);
+    const bool too_big = o.too_big;
+    if (e == hipSuccess) e = hipEventRecord(e2, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    memset(out, 0, sizeof *out);
+    if (e == hipSuccess) (void)hipEventElapsedTime(&out->ms, e1, e2);
+    (void)hipEventDestroy(e1);
+    (void)hipEventDestroy(e2);
+    // (never a null array: an empty vector's data() may be)
+    static const uint8_t none8[1] = {0};
+    static const uint32_t none32[2] = {0, 0};
+    if (e != hipSuccess) {
+        o.clear(0);
+        out->nonadj = out->comp_nonadj = out->wit_type = none8;
+        out->comp_label = out->wit_off = out->wit_txn = none32;
+        if (too_big) return fail(c, HSC_EINVAL, "the product graph does not fit 32-bit node or edge ids");
+    }
+    HIPCHK(c, e);
+    out->ntxn = nn;
+    out->nonadj = o.nonadj.empty() ? none8 : o.nonadj.data();
+    out->ncomp = (uint32_t)o.comp_label.size();
+    out->comp_label = o.comp_label.empty() ? none32 : o.comp_label.data();
+    out->comp_nonadj = o.comp_nonadj.empty() ? none8 : o.comp_nonadj.data();
+    if (o.wit_off.size() != (size_t)out->ncomp + 1) o.wit_off.assign((size_t)out->ncomp + 1, 0);
+    out->wit_off = o.wit_off.data();
+    out->wit_txn = o.wit_txn.empty() ? none32 : o.wit_txn.data();
+    out->wit_type = o.wit_type.empty() ? none8 : o.wit_type.data();
+    out->comps = o.comps;
+    out->txns = o.txns;
+    out->core_nodes = o.core_nodes;
+    out->product_nodes = o.product_nodes;
+    out->product_edges = o.product_edges;
+    out->scc_rounds = o.scc_rounds;
+    out->scc_iterations = o.scc_iterations;
     out->bfs_levels = o.bfs_levels;
     return HSC_OK;
 }

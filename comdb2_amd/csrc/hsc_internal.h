@@ -616,14 +616,25 @@ hipError_t realtime_stage(uint32_t n, const uint64_t *invoke, const uint64_t *co
 // Anomaly classes and witness cycles of a full build (hsc_anomaly.hip): the
 // analysis keeps its own buffers, so the build's edges and CSR stay as they
 // are (graph_scc's labels in g.scc are recomputed).
-struct AnomBufs {
+// The core both analyses start from (graph_core): the txns of components of
+// >= 2 txns relabelled densely, the edges inside a component as a typed CSR,
+// their E1 / anti split.
+struct CoreBufs {
     DBuf flag, id, node_txn, root, cid, comp_of, comp_label;  // core nodes and components
     DBuf eflag, epos, csrc, cdst, ctype, coff;                // core edges (typed CSR)
-    DBuf f1, fa, s1, e1i, aa, ab, ae, closed;                 // E1 rows, anti edges
+    DBuf f1, fa, s1, e1i, aa, ab, ae;                         // E1 rows, anti edges
+    DBuf scratch;
+    GraphBufs e1;  // the core restricted to E1: CSR / CSC and graph_scc's arrays
+    void release_core();
+};
+struct CoreDims {
+    uint32_t nc, ncomp, me, m1, na;  // core nodes, components, core edges, E1 / anti among them
+};
+struct AnomBufs : CoreBufs {
+    DBuf closed;                                              // anti edges a -> b with b ~> a over E1
     DBuf F, B, gs, g1c, cg2, cls;                             // reach masks, per-node bits
     DBuf wmin, wsrc, wtgt, wmask, pedge, target, front, front2;  // witness BFS
-    DBuf scratch, cnt;
-    GraphBufs e1;  // the core restricted to E1: CSR / CSC and graph_scc's arrays
+    DBuf cnt;
     void release_all();
 };
 struct AnomOut {  // host results (hsc_anomalies points into them)
@@ -650,6 +661,46 @@ struct AnomOut {  // host results (hsc_anomalies points into them)
 // component.
 hipError_t graph_anomalies(uint32_t nnodes, GraphBufs &g, AnomBufs &a, bool witness, uint32_t max_batches,
                            AnomOut &out, hipStream_t s);
+// graph_scc of the build (labels in g.scc) and the core of its components of
+// >= 2 txns; d.nc == 0: there is none and nothing else was written.
+hipError_t graph_core(uint32_t nnodes, GraphBufs &g, CoreBufs &a, CoreDims &d, uint32_t *rounds,
+                      uint32_t *iterations, hipStream_t s);
+// flag[v] = 1 for the members of label[]'s components of >= 2 nodes (flag zeroed by the caller)
+hipError_t scc_members(uint32_t n, const uint32_t *label, uint32_t *flag, hipStream_t s);
+// Snapshot isolation over the same typed edges (hsc_si.hip):
+// the txns on a closed walk without two cyclically consecutive anti edges.
+// Its core and product graph live in buffers of its own, so the build and
+// AnomBufs stay as they are (graph_scc's labels in g.scc are recomputed).
+struct SiBufs {
+    CoreBufs core;
+    GraphBufs p;   // the product graph: CSR / CSC and graph_scc's arrays over 2 nc nodes
+    DBuf pm, nonadj, cflag;                      // P-component members, per core node / component bits
+    DBuf wmin, wsrc, wtgt, par, target, front, front2, cnt;  // witness BFS over P
+    void release_all();
+};
+struct SiOut {  // host results (hsc_si_report points into them)
+    std::vector<uint8_t> nonadj, comp_nonadj, wit_type;
+    std::vector<uint32_t> comp_label, wit_off, wit_txn;
+    uint32_t comps, txns, core_nodes, product_nodes, scc_rounds, scc_iterations, bfs_levels;
+    uint64_t product_edges;
+    bool too_big;  // the product graph's ids do not fit 32 bits (graph_si: hipErrorInvalidValue)
+    void clear(uint32_t ntxn)
+    {
+        too_big = false;
+        nonadj.assign(ntxn, 0);
+        comp_nonadj.clear();
+        wit_type.clear();
+        comp_label.clear();
+        wit_off.assign(1, 0);
+        wit_txn.clear();
+        comps = txns = core_nodes = product_nodes = scc_rounds = scc_iterations = bfs_levels = 0;
+        product_edges = 0;
+    }
+};
+// hipErrorInvalidValue with out.too_big: the product graph's nodes or edges do
+// not fit 32 bits (nothing of it was launched).  witness: one cycle per
+// flagged component.
+hipError_t graph_si(uint32_t nnodes, GraphBufs &g, SiBufs &si, bool witness, SiOut &out, hipStream_t s);
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {
@@ -925,6 +976,7 @@ hipError_t warm_edges();
 hipError_t warm_graph();
 hipError_t warm_realtime();
 hipError_t warm_anomaly();
+hipError_t warm_si();
 hipError_t warm_route();
 
 }  // namespace hsc

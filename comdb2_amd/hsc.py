@@ -121,6 +121,19 @@ class Anomalies(C.Structure):
                 ("sweeps", C.c_uint32), ("bfs_levels", C.c_uint32), ("ms", C.c_float)]
 
 
+SI_WITNESS = 1  # hsc_dep_graph_si flags
+
+
+class SiReport(C.Structure):
+    """hsc_si_report: the arrays are host memory of the context."""
+    _fields_ = [("ntxn", C.c_uint32), ("nonadj", _p), ("ncomp", C.c_uint32), ("comp_label", _p),
+                ("comp_nonadj", _p), ("wit_off", _p), ("wit_txn", _p), ("wit_type", _p),
+                ("comps", C.c_uint32), ("txns", C.c_uint32), ("core_nodes", C.c_uint32),
+                ("product_nodes", C.c_uint32), ("product_edges", C.c_uint64),
+                ("scc_rounds", C.c_uint32), ("scc_iterations", C.c_uint32), ("bfs_levels", C.c_uint32),
+                ("ms", C.c_float)]
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -192,7 +205,7 @@ EXPORTS = [
     "hsc_set_autocollect",
     "hsc_small_stats", "hsc_harness_concurrent",
     "hsc_dep_graph_build", "hsc_dep_graph_stage_rw_pairs", "hsc_dep_graph_stage_realtime", "hsc_dep_graph_scc_built", "hsc_dep_graph_build_device", "hsc_dep_graph_cover", "hsc_dep_graph_cut", "hsc_dep_graph_scc_cut",
-    "hsc_dep_graph_anomalies",
+    "hsc_dep_graph_anomalies", "hsc_dep_graph_si",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -281,6 +294,7 @@ def load() -> C.CDLL:
                                                  C.c_int, C.POINTER(GraphStats)]),
         "hsc_dep_graph_cut": (C.c_int, [_p, _p, _p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "hsc_dep_graph_anomalies": (C.c_int, [_p, C.c_uint, C.c_uint, C.POINTER(Anomalies)]),
+        "hsc_dep_graph_si": (C.c_int, [_p, C.c_uint, C.POINTER(SiReport)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
         "hsc_window_ingest_raw": (C.c_int, [_p, C.POINTER(_RawLog)]),
@@ -1108,6 +1122,37 @@ class Validator:
                "wit_txn": arr(a.wit_txn, nw, np.uint32), "wit_type": arr(a.wit_type, nw, np.uint8),
                "comps": [int(x) for x in a.comps], "txns": [int(x) for x in a.txns]}
         for k in ("anti_edges", "anti_tested", "core_nodes", "reach_batches", "sweeps", "bfs_levels", "ms"):
+            out[k] = getattr(a, k)
+        return out
+
+    def dep_graph_si(self, witness: bool = True) -> dict:
+        """Snapshot isolation of the last full build (hsc_dep_graph_si):
+        nonadj[ntxn] (the txn lies on a closed walk without two cyclically
+        consecutive anti edges), comp_label / comp_nonadj per component of
+        >= 2 txns (comp_label as dep_graph_anomalies), one witness cycle per
+        flagged component (wit_off, wit_txn, wit_type; empty without witness)
+        and the stats.  No flagged component: the history's dependency graph
+        is allowed under snapshot isolation (strong snapshot isolation when
+        the real-time order was staged); aborted and intermediate reads are
+        not modelled.  The arrays are copies."""
+        a = SiReport()
+        self._chk(self.lib.hsc_dep_graph_si(self.ctx, SI_WITNESS if witness else 0, C.byref(a)),
+                  "hsc_dep_graph_si")
+
+        def arr(p, n, dt):
+            if n == 0:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)),
+                                         shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+
+        nc = a.ncomp
+        off = arr(a.wit_off, nc + 1, np.uint32)
+        nw = int(off[-1])
+        out = {"nonadj": arr(a.nonadj, a.ntxn, np.uint8), "comp_label": arr(a.comp_label, nc, np.uint32),
+               "comp_nonadj": arr(a.comp_nonadj, nc, np.uint8), "wit_off": off,
+               "wit_txn": arr(a.wit_txn, nw, np.uint32), "wit_type": arr(a.wit_type, nw, np.uint8)}
+        for k in ("comps", "txns", "core_nodes", "product_nodes", "product_edges", "scc_rounds",
+                  "scc_iterations", "bfs_levels", "ms"):
             out[k] = getattr(a, k)
         return out
 

@@ -43,6 +43,13 @@ no writer produced are dropped and counted (``dangling``).  hsc_dep_graph_*
 then builds the WR / WW / RW edges and the SCCs; a nontrivial SCC is a
 dependency cycle (two ``:ok`` inserts of one G2 key form the 2-cycle of rw
 edges the G2 checker looks for).
+
+``check_edn(..., isolation=True)`` also answers whether a history that is not
+serializable is at least snapshot isolation (comdb2 ships that level as
+``enable_snapshot_isolation``; adya.clj's write skew is legal under it).  That
+verdict is the dependency-graph condition only -- every cycle has two adjacent
+anti-dependency edges -- over the committed txns: ``:fail`` ops are dropped by
+the conversion, so aborted and intermediate reads (G1a, G1b) are not modelled.
 """
 from __future__ import annotations
 
@@ -344,7 +351,50 @@ def anomaly_report(ops: JepsenOps, result: dict) -> dict:
             "cycles": cycles, "g2_keys": g2_illegal(ops)}
 
 
-def check_edn(validator, text: str, witness: bool = True, realtime: bool = False) -> dict:
+def isolation_report(ops: JepsenOps, result: dict, si: dict, strict: Optional[dict] = None,
+                     strict_si: Optional[dict] = None) -> dict:
+    """The snapshot-isolation part of a report (a pure function of its
+    arguments): ``result`` is ``Validator.dep_graph_anomalies()``'s dict and
+    ``si`` ``Validator.dep_graph_si()``'s, both of the plain build; ``strict``
+    / ``strict_si`` the same two of the build with the real-time order, when
+    there was one.  ``snapshot_isolation_valid`` -- no component holds a cycle
+    without two adjacent anti-dependency edges; ``si_cycles`` -- one entry per
+    flagged component, shaped as :func:`anomaly_report`'s ``cycles`` and built
+    from the SI witness, ``type`` "G-nonadjacent" when the component's plain
+    class is G2 (two or more anti edges, none adjacent), else the plain class
+    name; ``levels`` -- ``g1c_free`` (no txn on a cycle of ww / wr edges),
+    ``snapshot_isolation``, ``serializable``, with ``strict``
+    ``strict_serializable`` and with ``strict_si`` too
+    ``strong_snapshot_isolation``.  All of it is the dependency-graph
+    condition over committed txns: G1a / G1b are not modelled."""
+    labels = [int(x) for x in si.get("comp_label", ())]
+    flagged = [int(x) for x in si.get("comp_nonadj", ())]
+    plain = {int(l): int(k) for l, k in zip(result.get("comp_label", ()), result.get("comp_class", ()))}
+    off = [int(x) for x in si.get("wit_off", ())]
+    wt = [int(x) for x in si.get("wit_txn", ())]
+    wy = [int(x) for x in si.get("wit_type", ())]
+    if len(off) != len(labels) + 1:
+        off = [0] * (len(labels) + 1)
+    cycles = []
+    for i, (lab, f) in enumerate(zip(labels, flagged)):
+        if not f:
+            continue
+        k = plain[lab]
+        txns = wt[off[i]:off[i + 1]]
+        cycles.append({"type": "G-nonadjacent" if k == 4 else ANOMALY_NAMES[k], "label": lab, "txns": txns,
+                       "edge_types": [edge_type_name(t) for t in wy[off[i]:off[i + 1]]],
+                       "ops": [ops.txn_ops[t] for t in txns]})
+    levels = {"g1c_free": int(result["txns"][0]) == 0, "snapshot_isolation": not any(flagged),
+              "serializable": len(result.get("comp_label", ())) == 0}
+    if strict is not None:
+        levels["strict_serializable"] = len(strict.get("comp_label", ())) == 0
+        if strict_si is not None:
+            levels["strong_snapshot_isolation"] = not any(int(x) for x in strict_si.get("comp_nonadj", ()))
+    return {"snapshot_isolation_valid": not any(flagged), "si_cycles": cycles, "levels": levels}
+
+
+def check_edn(validator, text: str, witness: bool = True, realtime: bool = False,
+              isolation: bool = False) -> dict:
     """A Jepsen EDN history through the GPU: convert, build the typed graph,
     classify its cycles; :func:`anomaly_report`'s dict plus ``history`` (the
     :class:`JepsenOps`) and ``analysis`` (dep_graph_anomalies' dict).
@@ -361,14 +411,26 @@ def check_edn(validator, text: str, witness: bool = True, realtime: bool = False
     (their sorted types); ``realtime_analysis`` -- the second analysis dict
     plus ``edges`` (rt edges staged) and ``stage_ms`` (their device time).
     ``valid``, ``anomaly_types`` and ``cycles`` keep describing the plain
-    pass."""
+    pass.
+
+    ``isolation``: also the snapshot-isolation verdict of the plain pass
+    (``Validator.dep_graph_si``): the report gains :func:`isolation_report`'s
+    ``snapshot_isolation_valid``, ``si_cycles`` and ``levels``, and
+    ``si_analysis`` (dep_graph_si's dict).  With ``realtime`` as well the
+    analysis runs again on the real-time build and ``levels`` has
+    ``strong_snapshot_isolation``.  Aborted and intermediate
+    reads are not modelled (the module docstring)."""
     ops = history_from_jepsen_edn(text)
     validator.dep_graph_build(ops.history, full=True)
     result = validator.dep_graph_anomalies(witness=witness)
     report = anomaly_report(ops, result)
     report["history"] = ops
     report["analysis"] = result
+    si = validator.dep_graph_si(witness=witness) if isolation else None
     if not realtime:
+        if isolation:
+            report.update(isolation_report(ops, result, si))
+            report["si_analysis"] = si
         return report
     staged = validator.dep_graph_stage_realtime(ops.invoke, ops.complete)
     validator.dep_graph_build(ops.history, full=True)
@@ -384,6 +446,10 @@ def check_edn(validator, text: str, witness: bool = True, realtime: bool = False
     report["realtime_cycles"] = cycles
     report["realtime_anomaly_types"] = sorted({c["type"] for c in cycles})
     report["realtime_analysis"] = strict
+    if isolation:
+        strict_si = validator.dep_graph_si(witness=witness)
+        report.update(isolation_report(ops, result, si, strict, strict_si))
+        report["si_analysis"] = si
     return report
 
 

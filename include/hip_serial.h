@@ -872,6 +872,64 @@ typedef struct hsc_anomalies {
     float ms;                                     /* device time of the analysis, SCC included */
 } hsc_anomalies;
 int hsc_dep_graph_anomalies(hsc_ctx *ctx, unsigned flags, unsigned max_anti_batches, hsc_anomalies *out);
+/* Snapshot isolation from the same typed edges (the last HSC_GRAPH_FULL build,
+ * E1 = type & 11, an anti edge has type == 4 exactly, only edges whose ends
+ * share a component of scc[] matter).  A dependency graph is allowed under
+ * snapshot isolation iff every cycle has two adjacent anti-dependency edges
+ * (Cerone and Gotsman; Elle's G-nonadjacent), so the level is violated iff
+ * some cycle has no two cyclically consecutive anti edges: a cycle without an
+ * anti edge (G1c), with one (G-single), or with several, none adjacent
+ * (G-nonadjacent -- hsc_dep_graph_anomalies calls these G2 like plain write
+ * skew).
+ * Product graph P: txn v becomes (v,0) "reached by an E1 edge" and (v,1)
+ * "reached by an anti edge"; an E1 edge u -> v gives (u,0) -> (v,0) and
+ * (u,1) -> (v,0), an anti edge gives (u,0) -> (v,1) only.
+ *   nonadj[v] = 1 iff (v,0) or (v,1) lies in a strongly connected component
+ *               of P with >= 2 nodes -- iff v lies on a closed walk of the
+ *               build's edges in which no two cyclically consecutive edges
+ *               are anti edges (lift the walk by the type of each arriving
+ *               edge; self edges are dropped, so it has >= 2 txns).
+ *   comp_nonadj[i] = 1 iff a member of component i has the bit.  The
+ *               component then holds a simple cycle without two adjacent anti
+ *               edges (split a closed walk at a repeated txn: if one half has
+ *               two anti edges at the split, both edges of the other half
+ *               there are not anti edges; recurse on a good half).
+ * Every txn with the G1c or G-single bit of hsc_dep_graph_anomalies has the
+ * bit; a component of class G2 with the flag is G-nonadjacent; a component
+ * without the flag has class G2 and is legal under snapshot isolation (write
+ * skew only).  The answer is exact whatever max_anti_batches was given to
+ * hsc_dep_graph_anomalies: no reach budget enters here.
+ * Scope: this is the dependency-graph condition only.  The graph is built
+ * from committed txns; aborted and intermediate reads (G1a, G1b) are not
+ * modelled.  With a staged real-time order the definitions hold unchanged
+ * over the widened E1, and the verdict is strong snapshot isolation.
+ * HSC_SI_WITNESS: per flagged component one simple cycle of >= 2 of its txns,
+ * wit_txn[wit_off[i], wit_off[i + 1]), every step an edge of the build with
+ * its type bits in wit_type, no two cyclically consecutive steps anti edges.
+ * Which edge closes it and its length are unspecified.  An unflagged
+ * component has an empty run.
+ * comp_label equals hsc_anomalies.comp_label of the same build.  The arrays
+ * are host memory owned by the context, never NULL, valid until its next
+ * graph call; the results of hsc_dep_graph_anomalies stay valid across this
+ * call.  HSC_ESTATE after a raw build, HSC_EDEVICE on a host-only context,
+ * HSC_EINVAL for a NULL argument or a product graph (twice the txns in
+ * cycles; their edges plus their E1 edges) past 32-bit ids.  The sharded path
+ * (hsc_multi_graph_scc) has no such call: it keeps no typed edges. */
+#define HSC_SI_WITNESS 1              /* flags */
+typedef struct hsc_si_report {
+    uint32_t ntxn;   const uint8_t *nonadj;       /* [ntxn] the bit defined above */
+    uint32_t ncomp;  const uint32_t *comp_label;  /* [ncomp] ascending, = hsc_anomalies.comp_label */
+    const uint8_t *comp_nonadj;                   /* [ncomp] some member has the bit */
+    const uint32_t *wit_off;                      /* [ncomp+1]; empty run for an unflagged component; all 0 without the flag */
+    const uint32_t *wit_txn;                      /* cycle txns */
+    const uint8_t  *wit_type;                     /* type bits of edge wit_txn[i] -> next (cyclically) */
+    uint32_t comps, txns;                         /* flagged components / txns carrying the bit */
+    uint32_t core_nodes, product_nodes;           /* txns in cycles / nodes of P (twice as many) */
+    uint64_t product_edges;                       /* core edges + core E1 edges */
+    uint32_t scc_rounds, scc_iterations, bfs_levels;
+    float ms;                                     /* device time, both SCC runs included */
+} hsc_si_report;
+int hsc_dep_graph_si(hsc_ctx *ctx, unsigned flags, hsc_si_report *out);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst

@@ -1032,6 +1032,9 @@ static int device_build(hsc_ctx *c, size_t n_in)
                                          c->cdir, c->rank_lsn32, c->rank_base,
                                          c->d_key32.as<uint32_t>(), c->d_rank32.as<uint32_t>(),
                                          tiles_fused ? nullptr : tiles_flag, s));
+            HIPCHK(c, c->d_recent.ensure(4 * narrow_recent_words(wn.ntiles)));
+            HIPCHK(c, narrow_recent_build(c->d_key32.as<uint32_t>(), c->d_rank32.as<uint32_t>(),
+                                          (uint32_t)c->n, wn.ntiles, c->d_recent.as<uint32_t>(), s));
             HIPCHK(c, hipMemcpyAsync(&wide32, tiles_flag, 4, hipMemcpyDeviceToHost, s));  // read below
             tiles32 = true;
         }
@@ -1450,7 +1453,7 @@ static void swap_window(hsc_ctx *a, hsc_ctx *b)
     swap(a->ntiles32, b->ntiles32), swap(a->d_trad2, b->d_trad2), swap(a->d_commits, b->d_commits);
     swap(a->d_cdir, b->d_cdir), swap(a->d_tdir, b->d_tdir), swap(a->d_trad, b->d_trad);
     swap(a->d_trad16, b->d_trad16), swap(a->d_trad16b, b->d_trad16b), swap(a->trad_shift, b->trad_shift);
-    swap(a->d_key32, b->d_key32), swap(a->d_rank32, b->d_rank32);
+    swap(a->d_key32, b->d_key32), swap(a->d_rank32, b->d_rank32), swap(a->d_recent, b->d_recent);
     for (int i = 0; i < 4; ++i) swap(a->d_ctmp[i], b->d_ctmp[i]);
     swap(a->cdir, b->cdir), swap(a->tdir, b->tdir), swap(a->trad_m, b->trad_m);
     swap(a->trad_log, b->trad_log), swap(a->ncommit, b->ncommit), swap(a->has_commits, b->has_commits);
@@ -2606,6 +2609,12 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
     ntl.trad16 = c->trad_m ? c->d_trad16.as<uint16_t>() : nullptr;
     ntl.trad_shift = c->trad_shift;
     ntl.recs = c->w_trecs.as<uint4>();
+    narrow_recent_view(ntl, c->d_recent.as<uint32_t>(), wn.ntiles);
+    if (!c->d_fulljoins.p) {
+        HIPCHK(c, c->d_fulljoins.ensure(4));
+        HIPCHK(c, hipMemset(c->d_fulljoins.p, 0, 4));
+    }
+    work.full_joins = c->d_fulljoins.as<uint32_t>();
     // conflict flags: internal, all zero between batches (the pack clears them)
     const size_t had = c->w_vflags.bytes;
     HIPCHK(c, c->w_vflags.ensure((std::max<size_t>(b->n_txn, 1) + 15) & ~(size_t)15));
@@ -3399,7 +3408,7 @@ void hsc_ctx_destroy(hsc_ctx *c)
                     &c->w_bucket, &c->w_cursor, &c->w_items, &c->w_item_desc, &c->w_recs,
                     &c->d_nkeys, &c->d_nmaxs, &c->d_nbase, &c->d_nzero, &c->d_ntmax,
                     &c->d_nsp_g, &c->d_nsp_w, &c->d_ngs, &c->d_nscratch, &c->p_code_lo,
-                    &c->p_code_hi, &c->p_zero, &c->d_commits, &c->d_cdir, &c->d_tdir, &c->d_trad, &c->d_trad16, &c->d_trad16b, &c->d_done, &c->w_vflags, &c->d_key32, &c->d_rank32,
+                    &c->p_code_hi, &c->p_zero, &c->d_commits, &c->d_cdir, &c->d_tdir, &c->d_trad, &c->d_trad16, &c->d_trad16b, &c->d_done, &c->w_vflags, &c->d_key32, &c->d_rank32, &c->d_recent, &c->d_fulljoins,
                     &c->d_ctmp[0], &c->d_ctmp[1], &c->d_ctmp[2], &c->d_ctmp[3], &c->w_tcode,
                     &c->w_tcode2, &c->w_trecs};
     for (DBuf *b : bufs) b->release();
@@ -4487,6 +4496,13 @@ int hsc_batch_stats(hsc_ctx *c, hsc_batch_stats_t *out)
     out->plan_batches = c->nt_plan.load();
     out->fast_locates = c->nt_fast.load();
     out->general_locates = c->nt_general.load();
+    // the device counter as it stands (a batch still running may yet add to it)
+    uint32_t full = 0;
+    if (c->d_fulljoins.p) {
+        (void)hipSetDevice(c->device);
+        if (hipMemcpy(&full, c->d_fulljoins.p, 4, hipMemcpyDeviceToHost) != hipSuccess) full = 0;
+    }
+    out->full_tile_joins = full;
     return HSC_OK;
 }
 

@@ -256,6 +256,9 @@ struct ProbeWork {
     // path (null: none)
     uint64_t *hot;
     uint64_t batch;
+    // narrow join: blocks / items that staged a whole tile, not its recent list
+    // (cumulative, device memory; null: not counted)
+    uint32_t *full_joins;
 };
 // Diagnostic phase stamps (HSC_STAMPS builds only): thread 0 of a block
 // records s_memtime at phase boundaries into a buffer of its own (never an
@@ -380,12 +383,23 @@ struct NarrowTiles {
                                // locate stages into LDS
     int trad_shift;            // trad[m + 1], read back by the host after the build
     uint4 *recs;               // chunk areas of 2 x chunk records {lo delta, hi delta, r(S), read set}
+    // recent lists (k_recent): per tile its 256 newest rows -- keys as a
+    // 256-entry Eytzinger tree, ranks in key order -- and the largest rank
+    // of a row left out: a record with r(S) >= rtheta[t] needs the list only
+    const uint32_t *rkey32, *rrank32;  // [ntiles][256]
+    const uint32_t *rtheta;            // [ntiles]
 };
 hipError_t check_sorted_u64(const uint64_t *v, size_t n, uint32_t *flag, hipStream_t s);
 // rank32 by a search of cdir (the 16-ary directory over the commit LSNs C)
 hipError_t narrow_tiles_build(const uint64_t *key64, const uint64_t *lsn, uint32_t n, uint32_t len,
                               const Dir16 &cdir, int rank_lsn32, uint64_t rank_base,
                               uint32_t *key32, uint32_t *rank32, uint32_t *flag, hipStream_t s);
+// The tiles' recent lists from final key32 / rank32 (either rank mode) into
+// `recent`, narrow_recent_words(ntiles) u32s; narrow_recent_view points nt at them.
+size_t narrow_recent_words(uint32_t ntiles);
+hipError_t narrow_recent_build(const uint32_t *key32, const uint32_t *rank32, uint32_t n, uint32_t ntiles,
+                               uint32_t *recent, hipStream_t s);
+void narrow_recent_view(NarrowTiles &nt, const uint32_t *recent, uint32_t ntiles);
 // r(S) of lsn32 mode: lsn > S <=> lsn - base + 1 > r(S)
 __host__ __device__ inline uint32_t lsn32_rank(uint64_t S, uint64_t base)
 {

@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace hsc {
 
@@ -150,6 +151,9 @@ hipError_t narrow_end_rows(const WinView &w, const uint32_t *n_dev, uint64_t *ou
 namespace {
 constexpr uint32_t kNoTile32 = 0xFFFFFFFFu;
 constexpr int kTLog2 = 12;  // 4096-row tiles (= the code view's tiles)
+constexpr int kRecentLog2 = 8;  // a tile's recent list: its R newest rows (k_recent)
+constexpr uint32_t kRecent = 1u << kRecentLog2;  // R = 256
+static_assert(kRecentLog2 < kTLog2 && kRecent == 4 * 64, "the join's wave 0 stages a list, a quad per lane");
 }  // namespace
 
 // Eytzinger (BFS) slot of sorted row r of a 4096-row tile: rows 0 .. 4094
@@ -1032,6 +1036,135 @@ hipError_t narrow_tiles_build(const uint64_t *key64, const uint64_t *lsn, uint32
             lsn, n, len, cdir, rank32);
     }
     return hipGetLastError();
+}
+
+// ---- recent lists ----
+// The kRecent (R) newest rows of every tile, for the join (join_s_item):
+//   members  the min(R, tn) rows of the tile's tn with the largest rank32; ties
+//            at the cut go to the smaller key (the earlier row);
+//   rkey32   their key32 in key order, laid out as a 256-entry Eytzinger tree
+//            (sorted position i at eyt8(i)); rrank32 their ranks in key order;
+//            a short list is padded with key ~0 and rank 0 (row ranks start at
+//            1), so a pad is above every bound and older than every snapshot;
+//   rtheta   the largest rank32 of a row left out, 0 if none is.
+// Every row of the tile with rank32 > rtheta is a member (a row left out has
+// rank <= rtheta), which is all the join needs to know.
+// One workgroup per tile, after key32 / rank32 are final (either rank mode):
+// thread t holds rows 4t .. 4t + 3 (ranks lie in row order), the R-th largest
+// rank is selected bit by bit from the top (a block count per bit), the rows
+// equal to it and then the members are numbered by block scans in row order.
+__device__ __forceinline__ uint32_t eyt8(uint32_t r)
+{
+    const uint32_t i = r + 1;
+    const int tz = __builtin_ctz(i);
+    return i == kRecent ? 0 : (1u << (kRecentLog2 - 1 - tz)) + (i >> (tz + 1));
+}
+
+constexpr int kRecentThreads = (1 << kTLog2) / 4;
+// exclusive scan of x over the block's threads; ws: a wave-total array of its own
+__device__ __forceinline__ uint32_t recent_scan(uint32_t x, uint32_t *ws)
+{
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t s = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(s, o, 64);
+        if (lane >= (uint32_t)o) s += y;
+    }
+    if (lane == 63) ws[wave] = s;
+    __syncthreads();
+    uint32_t run = s - x;
+    for (uint32_t w = 0; w < wave; ++w) run += ws[w];
+    return run;
+}
+
+__global__ __launch_bounds__(kRecentThreads) void k_recent(const uint32_t *key32, const uint32_t *rank32,
+                                                           uint32_t n, uint32_t *rkey32, uint32_t *rrank32,
+                                                           uint32_t *rtheta)
+{
+    constexpr uint32_t T = 1u << kTLog2;
+    __shared__ __attribute__((aligned(16))) uint32_t sk[T];  // the tile's keys as stored (eyt12 order)
+    __shared__ uint32_t cnt[32], ws[2][kRecentThreads / 64], lk[kRecent], lr[kRecent], theta;
+    const uint32_t tile = blockIdx.x, t = threadIdx.x, lane = t & 63;
+    const size_t ts = (size_t)tile << kTLog2;
+    const uint32_t tn = min(T, n - (tile << kTLog2));
+    const u32x4 rq = *(const u32x4 *)(rank32 + ts + 4 * t);
+    ((u32x4 *)sk)[t] = *(const u32x4 *)(key32 + ts + 4 * t);
+    const uint32_t rv[4] = {rq.x, rq.y, rq.z, rq.w};
+    if (t < 32) cnt[t] = 0;
+    if (t < kRecent) lk[t] = 0xFFFFFFFFu, lr[t] = 0;
+    if (t == 0) theta = 0;
+    __syncthreads();
+    // v = the R-th largest rank, take = how many of the rows equal to v are
+    // members (tn <= R: every row is one -- pads have rank 0, rows >= 1)
+    uint32_t v = 0, take = kRecent;
+    if (tn > kRecent) {
+        for (int b = 31; b >= 0; --b) {
+            // rows that agree with v above bit b and have bit b set
+            const uint32_t want = v >> b | 1;
+            uint32_t c = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c += (rv[k] >> b) == want;
+#pragma unroll
+            for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o, 64);
+            if (lane == 0 && c) atomicAdd(&cnt[b], c);
+            __syncthreads();
+            const uint32_t c1 = cnt[b];
+            if (c1 >= take)
+                v |= 1u << b;
+            else
+                take -= c1;
+        }
+    }
+    bool eq[4];
+    uint32_t ne = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) eq[k] = 4 * t + k < tn && rv[k] == v, ne += eq[k];
+    uint32_t ei = recent_scan(ne, ws[0]);
+    bool mem[4];
+    uint32_t nm = 0, out = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        mem[k] = 4 * t + k < tn && (rv[k] > v || (eq[k] && ei < take));
+        ei += eq[k];
+        nm += mem[k];
+        if (4 * t + k < tn && !mem[k]) out = max(out, rv[k]);
+    }
+    uint32_t pos = recent_scan(nm, ws[1]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (mem[k]) {
+            lk[eyt8(pos)] = sk[eyt12(4 * t + k)];
+            lr[pos] = rv[k];
+            ++pos;
+        }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) out = max(out, (uint32_t)__shfl_xor((int)out, o, 64));
+    if (lane == 0 && out) atomicMax(&theta, out);
+    __syncthreads();
+    if (t < kRecent) {
+        rkey32[(size_t)tile * kRecent + t] = lk[t];
+        rrank32[(size_t)tile * kRecent + t] = lr[t];
+    }
+    if (t == 0) rtheta[tile] = theta;
+}
+
+size_t narrow_recent_words(uint32_t ntiles) { return (size_t)ntiles * (2 * kRecent + 1); }
+
+hipError_t narrow_recent_build(const uint32_t *key32, const uint32_t *rank32, uint32_t n, uint32_t ntiles,
+                               uint32_t *recent, hipStream_t s)
+{
+    if (ntiles == 0) return hipSuccess;
+    uint32_t *rkey = recent, *rrank = rkey + (size_t)ntiles * kRecent, *rtheta = rrank + (size_t)ntiles * kRecent;
+    k_recent<<<ntiles, kRecentThreads, 0, s>>>(key32, rank32, n, rkey, rrank, rtheta);
+    return hipGetLastError();
+}
+
+void narrow_recent_view(NarrowTiles &nt, const uint32_t *recent, uint32_t ntiles)
+{
+    nt.rkey32 = recent;
+    nt.rrank32 = recent + (size_t)ntiles * kRecent;
+    nt.rtheta = nt.rrank32 + (size_t)ntiles * kRecent;
 }
 
 // ---- 16-ary directories over sorted u64 arrays ----
@@ -1974,27 +2107,30 @@ hipError_t launch_plan_s(const ProbeWork &work, uint32_t ntiles, uint32_t *ctl, 
 }
 
 // ---- join: 8-byte rows ----
-// Row quad v of thread t = rows 4 (t + kJoinThreads v) .. + 3: one 16-byte
-// load of keys (already in Eytzinger order, k_key32) and one of ranks per
-// quad, stored to LDS as they are; 16-row maxima over 4 lanes, 128-row maxima
-// over 32 lanes.
+// A block stages its tile's recent list (wave 0: a quad of keys, already in
+// Eytzinger order, and one of ranks per lane) and only for old snapshots the
+// whole tile (below) -- row quad v of thread t = rows 4 (t + kJoinThreads v)
+// .. + 3: one 16-byte load of keys (k_key32's order) and one of ranks per
+// quad.  Either way the quads are stored to LDS as they are, with 16-row
+// maxima over 4 lanes and 128-row maxima over 32 lanes.
 
 // The join is held to 8 waves per SIMD: at 85-99 SGPRs the hardware admits
 // only 6-7 (measured on config 2: join 34 -> 31.7 us, one stream 71.3 -> 69 us)
 // Chunk-sorted records: record j of tile t lives in the
 // run of the chunk g whose offset inside the tile (the plan's scan of column
 // t) is the last one <= j, at chunk g's area + cst[t][g] + (j - that offset).
-// The tile's column is staged first (its loads ahead of the rows'), each
+// The tile's column is staged first (its loads ahead of the list's), each
 // thread finds its records' chunks by a 9-step search of it in LDS and issues
-// the record loads while the rows are still arriving.
+// the record loads.
 // kJoinCol (no plan ran): the block reads column `tile` of the locate's
 // chunk-major table itself -- thread g the entry of chunk g, 4-byte loads that
 // the tiles sharing a line of a chunk row (neighbours on one XCD) find in its
 // L2 after the first touch (the table in pieces of 4 tiles, a column 16 bytes
 // apart, measured the same: 41.3 vs 41.5 us per two-stream step, within the
 // spread) -- and scans the counts over its 8 waves: Es, Cs, the tile's total.
-// It runs every record of the tile, kJoinChunk a round; rows, maxima and the
-// column are staged once and only read afterwards.
+// It runs every record of the tile, kJoinChunk a round; the list, the column
+// and (once a round needs it) the tile's rows are staged once and only read
+// afterwards.
 enum JoinMode { kJoinItem, kJoinTile, kJoinCol };
 
 // Read set i's flag of the locate into its verdict byte and bitmap bit; set
@@ -2011,11 +2147,26 @@ __device__ __forceinline__ void move_flag(const ProbeWork &work, uint8_t *flags,
     }
 }
 
+// The rows a join block stages.  Exactness rule of the recent list (k_recent):
+// if r(S) >= rtheta[t], every row of tile t with rank32 > r(S) is a list
+// member -- a row left out has rank32 <= rtheta[t] <= r(S), ties included --
+// so "some member has lo <= key <= hi and rank32 > r(S)" is the whole tile's
+// answer.  A block therefore stages the tile's list (2 KB) and walks its
+// records over it, 8 levels instead of 12, as long as every live record of
+// the round has r(S) >= rtheta[t]: one block-wide vote per round.  The first
+// round that fails the vote stages the whole tile (32 KB, into
+// arrays of its own, so the list's readers need no barrier), counts itself in
+// work.full_joins, and the tile stays staged for the item's remaining rounds.
+struct JoinLds {
+    uint32_t *keys, *rank, *b16, *b128;      // the whole tile
+    uint32_t *lkeys, *lrank, *lb16, *lb128;  // its recent list
+    uint32_t *Es, *Cs, *vote;  // vote[2]: a round's "stage the whole tile"
+};
+
 template <JoinMode kMode>
 __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowTiles &nt,
                                             uint32_t n, uint32_t xi, uint8_t *verdict,
-                                            uint32_t *keys, uint32_t *rank, uint32_t *b16,
-                                            uint32_t *b128, uint32_t *Es, uint32_t *Cs,
+                                            const JoinLds &L,
                                             uint32_t rs = 0, uint8_t *flags = nullptr,
                                             uint32_t *wtot = nullptr)
 {
@@ -2023,6 +2174,7 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
     constexpr int RQ = T / (4 * kJoinThreads);
     constexpr int kRec = kJoinChunk / kJoinThreads;
     static_assert(kMaxChunks <= kJoinThreads, "one column entry per thread");
+    uint32_t *const Es = L.Es, *const Cs = L.Cs;
     uint32_t tile, j0, j1;
     if constexpr (kMode != kJoinItem) {
         tile = xi, j0 = 0;
@@ -2033,7 +2185,7 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
     const uint32_t G = work.G;
     uint32_t e = 0, cs = 0;
     // this block's share of the flags: the first stride's load goes out ahead
-    // of the column's and the rows'
+    // of the column's and the list's
     const uint32_t fstride = gridDim.x * kJoinThreads, fi = blockIdx.x * kJoinThreads + threadIdx.x;
     uint8_t f0 = 0;
     if constexpr (kMode == kJoinCol) {
@@ -2046,14 +2198,15 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
             cs = work.cst[col + threadIdx.x];
         }
     }
-    u32x4 rk[RQ], rr[RQ], rec[kRec];
-    const size_t ts = (size_t)tile << kTLog2;
-#pragma unroll
-    for (int v = 0; v < RQ; ++v) {
-        const size_t row = ts + 4 * (threadIdx.x + kJoinThreads * v);
-        rk[v] = *(const u32x4 *)(nt.key32 + row);
-        rr[v] = *(const u32x4 *)(nt.rank32 + row);
+    // the tile's list: wave 0, a quad of keys and one of ranks per lane
+    const uint32_t theta = sload(nt.rtheta + tile);
+    u32x4 lk = {0, 0, 0, 0}, lr = {0, 0, 0, 0};
+    if (threadIdx.x < kRecent / 4) {
+        const size_t q = (size_t)tile * kRecent + 4 * threadIdx.x;
+        lk = *(const u32x4 *)(nt.rkey32 + q);
+        lr = *(const u32x4 *)(nt.rrank32 + q);
     }
+    u32x4 rec[kRec];
     if constexpr (kMode == kJoinCol) {
         move_flag(work, flags, verdict, fi, f0);
         // (a batch of more read sets than the grid has threads: four loads in flight)
@@ -2092,6 +2245,22 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
     }
     if constexpr (kMode == kJoinTile) j1 = min(kTileCap, sload(work.counts + tile));
     if (kMode == kJoinCol || threadIdx.x < G) Es[threadIdx.x] = e, Cs[threadIdx.x] = cs;
+    // a quad's ranks into 16-row maxima (4 lanes) and 128-row maxima (32 lanes)
+    auto maxima = [](const u32x4 &r, uint32_t quad, uint32_t *b16, uint32_t *b128) {
+        uint32_t m = max(max(r.x, r.y), max(r.z, r.w));
+        m = max(m, (uint32_t)__shfl_xor((int)m, 1, 64));
+        m = max(m, (uint32_t)__shfl_xor((int)m, 2, 64));
+        if ((threadIdx.x & 3) == 0) b16[quad >> 2] = m;
+#pragma unroll
+        for (int d = 4; d < 32; d <<= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+        if ((threadIdx.x & 31) == 0) b128[quad >> 5] = m;
+    };
+    if (threadIdx.x < kRecent / 4) {  // (wave 0 as a whole)
+        ((u32x4 *)L.lkeys)[threadIdx.x] = lk;
+        ((u32x4 *)L.lrank)[threadIdx.x] = lr;
+        maxima(lr, threadIdx.x, L.lb16, L.lb128);
+        if (threadIdx.x < 2) L.vote[threadIdx.x] = 0;
+    }
     __syncthreads();
     HSC_STAMP(work, 1, 1);
     const size_t area = 2 * (size_t)work.chunk;
@@ -2110,24 +2279,33 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
                             : u32x4{0, 0, 0, 0};
         }
     };
-    fetch(j0);
+    // the whole tile: rows and maxima to LDS as they lie (today's staging)
+    auto stage_tile = [&]() {
+        u32x4 rk[RQ], rr[RQ];
+        const size_t ts = (size_t)tile << kTLog2;
 #pragma unroll
-    for (int v = 0; v < RQ; ++v) {
-        const uint32_t quad = threadIdx.x + kJoinThreads * v;
-        ((u32x4 *)keys)[quad] = rk[v];
-        ((u32x4 *)rank)[quad] = rr[v];
-        uint32_t m = max(max(rr[v].x, rr[v].y), max(rr[v].z, rr[v].w));
-        m = max(m, (uint32_t)__shfl_xor((int)m, 1, 64));
-        m = max(m, (uint32_t)__shfl_xor((int)m, 2, 64));
-        if ((threadIdx.x & 3) == 0) b16[quad >> 2] = m;
+        for (int v = 0; v < RQ; ++v) {
+            const size_t row = ts + 4 * (threadIdx.x + kJoinThreads * v);
+            rk[v] = *(const u32x4 *)(nt.key32 + row);
+            rr[v] = *(const u32x4 *)(nt.rank32 + row);
+        }
 #pragma unroll
-        for (int d = 4; d < 32; d <<= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
-        if ((threadIdx.x & 31) == 0) b128[quad >> 5] = m;
-    }
-    __syncthreads();
-    HSC_STAMP(work, 1, 2);
+        for (int v = 0; v < RQ; ++v) {
+            const uint32_t quad = threadIdx.x + kJoinThreads * v;
+            ((u32x4 *)L.keys)[quad] = rk[v];
+            ((u32x4 *)L.rank)[quad] = rr[v];
+            maxima(rr[v], quad, L.b16, L.b128);
+        }
+        if (threadIdx.x == 0 && work.full_joins) atomicAdd(work.full_joins, 1u);
+        __syncthreads();
+    };
     const uint32_t tn = min(T, n - (tile << kTLog2));
-    auto walk = [&](uint32_t r0) {
+    // records r0 .. of the round over a sorted run of nrow rows staged as a
+    // 2^LV-entry Eytzinger tree (keys), ranks in row order and their maxima
+    auto walk = [&](uint32_t r0, auto lv, const uint32_t *keys, const uint32_t *rank,
+                    const uint32_t *b16, const uint32_t *b128, uint32_t nrow) {
+        constexpr int LV = decltype(lv)::value;
+        constexpr uint32_t N = 1u << LV;
 #pragma unroll
         for (int k = 0; k < kRec; ++k) {
             const uint32_t j = r0 + k * kJoinThreads + threadIdx.x;
@@ -2137,14 +2315,14 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
             const uint32_t lo = rec[k].x, hi = rec[k].y, rs = rec[k].z;
             uint32_t ja = 1, jb = 1;
 #pragma unroll
-            for (int d = 0; d < kTLog2; ++d) {
+            for (int d = 0; d < LV; ++d) {
                 const uint32_t ka = keys[ja], kb = keys[jb];
                 ja = 2 * ja + (ka < lo);
                 jb = 2 * jb + (kb <= hi);
             }
             const uint32_t kl = keys[0];
-            const uint32_t pa = min(ja - T + (kl < lo), tn);
-            const uint32_t pb = min(jb - T + (kl <= hi), tn);
+            const uint32_t pa = min(ja - N + (kl < lo), nrow);
+            const uint32_t pb = min(jb - N + (kl <= hi), nrow);
             if (wave_any_after32(rank, b16, b128, pa, pb, rs, j < j1 && pa < pb)) {
                 // (r05w, world-1 per-rank step: these atomics 50.7 / 51.9 us per
                 // step, guarded by a read of the verdict byte 53.3 / 52.5, the
@@ -2155,12 +2333,33 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
             }
         }
     };
-    walk(j0);
-    if constexpr (kMode == kJoinCol) {  // a hot tile: the rounds past the first
-        for (uint32_t jb = kJoinChunk; jb < j1; jb += kJoinChunk) {
-            fetch(jb);
-            walk(jb);
+    bool full = false;  // block-uniform: the whole tile is staged
+    auto round = [&](uint32_t jb) {
+        fetch(jb);
+        if (!full) {
+            // a live record whose snapshot is older than a row left out of the list?
+            bool old = false;
+#pragma unroll
+            for (int k = 0; k < kRec; ++k)
+                old |= jb + k * kJoinThreads + threadIdx.x < j1 && rec[k].x <= rec[k].y && rec[k].z < theta;
+            // (a slot per round parity: a wave already in the next round's vote
+            // must not change what a slower wave still has to read of this one's)
+            uint32_t *vote = L.vote + (jb / kJoinChunk & 1);
+            if (__ballot(old) && (threadIdx.x & 63) == 0) *vote = 1;
+            __syncthreads();
+            full = __builtin_amdgcn_readfirstlane(*vote) != 0;
+            if (full) stage_tile();
         }
+        if (jb == j0) HSC_STAMP(work, 1, 2);
+        if (full)
+            walk(jb, std::integral_constant<int, kTLog2>{}, L.keys, L.rank, L.b16, L.b128, tn);
+        else
+            walk(jb, std::integral_constant<int, kRecentLog2>{}, L.lkeys, L.lrank, L.lb16, L.lb128,
+                 min(kRecent, tn));
+    };
+    round(j0);
+    if constexpr (kMode == kJoinCol) {  // a hot tile: the rounds past the first
+        for (uint32_t jb = kJoinChunk; jb < j1; jb += kJoinChunk) round(jb);
     }
 }
 
@@ -2180,7 +2379,11 @@ __global__ __launch_bounds__(kJoinThreads) __attribute__((amdgpu_waves_per_eu(8,
     __shared__ __attribute__((aligned(16))) uint32_t rank[T];
     __shared__ uint32_t b16[T / 16];
     __shared__ uint32_t b128[T / 128];
-    __shared__ uint32_t Es[kMaxChunks], Cs[kMaxChunks];
+    __shared__ __attribute__((aligned(16))) uint32_t lkeys[kRecent];
+    __shared__ __attribute__((aligned(16))) uint32_t lrank[kRecent];
+    __shared__ uint32_t lb16[kRecent / 16], lb128[kRecent / 128];
+    __shared__ uint32_t Es[kMaxChunks], Cs[kMaxChunks], vote[2];
+    const JoinLds L{keys, rank, b16, b128, lkeys, lrank, lb16, lb128, Es, Cs, vote};
 
     HSC_STAMP(work, 1, 0);
     // chunk-sorted records: neighbouring tiles on one XCD (their runs of a
@@ -2190,7 +2393,7 @@ __global__ __launch_bounds__(kJoinThreads) __attribute__((amdgpu_waves_per_eu(8,
         __shared__ uint32_t wtot[kJoinThreads / 64];
         const uint32_t tile = xcd_chunk(blockIdx.x, tb / 8);
         if (tile < ntiles) {
-            join_s_item<kJoinCol>(work, nt, n, tile, verdict, keys, rank, b16, b128, Es, Cs,
+            join_s_item<kJoinCol>(work, nt, n, tile, verdict, L,
                                   (ntiles + 3) & ~3u, flags, wtot);
         } else {
             for (uint32_t i = blockIdx.x * kJoinThreads + threadIdx.x; i < work.n_txn;
@@ -2199,13 +2402,13 @@ __global__ __launch_bounds__(kJoinThreads) __attribute__((amdgpu_waves_per_eu(8,
         }
     } else if (blockIdx.x < tb) {
         const uint32_t tile = xcd_chunk(blockIdx.x, tb / 8);
-        if (tile < ntiles) join_s_item<kJoinTile>(work, nt, n, tile, verdict, keys, rank, b16, b128, Es, Cs);
+        if (tile < ntiles) join_s_item<kJoinTile>(work, nt, n, tile, verdict, L);
     } else {  // blocks past the tiles take the hot tiles' overflow items in turn
         const uint32_t nextra = work.item_off[1];
         const uint32_t stride = gridDim.x - tb;
         for (uint32_t xi = blockIdx.x - tb; xi < nextra; xi += stride) {
             __syncthreads();  // the previous item's LDS reads are done
-            join_s_item<kJoinItem>(work, nt, n, xi, verdict, keys, rank, b16, b128, Es, Cs);
+            join_s_item<kJoinItem>(work, nt, n, xi, verdict, L);
         }
     }
     HSC_STAMP(work, 1, 3);

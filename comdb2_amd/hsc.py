@@ -161,7 +161,8 @@ class SmallStats(C.Structure):
 class BatchStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("marshals", "read_sets", "ranges", "parts_ns", "alloc_ns",
                                           "assemble_ns", "launch_ns", "wait_ns", "column_batches",
-                                          "plan_batches", "fast_locates", "general_locates")]
+                                          "plan_batches", "fast_locates", "general_locates",
+                                          "full_tile_joins")]
 
 
 class ProtocolTxn(C.Structure):

@@ -476,12 +476,17 @@ int hsc_small_stats(hsc_ctx *ctx, hsc_small_stats_t *out);
  * next 64 down the plan path).  fast_locates / general_locates: launches of
  * the narrow-tile locate by instance -- one built for the window's shape (1
  * or 2 key words, the last one varying, bucket table, no compressed codes,
- * 32-bit commit ranks) / the one that reads the shape at run time. */
+ * 32-bit commit ranks) / the one that reads the shape at run time.
+ * full_tile_joins: join blocks and overflow items of the narrow tiles that
+ * staged a whole 4096-row tile because a record's snapshot was older than a
+ * row outside the tile's recent list (the rest answered from the list of the
+ * tile's 256 newest rows); a device counter, read when this is called. */
 typedef struct hsc_batch_stats_t {
     uint64_t marshals, read_sets, ranges;
     uint64_t parts_ns, alloc_ns, assemble_ns, launch_ns, wait_ns;
     uint64_t column_batches, plan_batches;
     uint64_t fast_locates, general_locates;
+    uint64_t full_tile_joins;
 } hsc_batch_stats_t;
 int hsc_batch_stats(hsc_ctx *ctx, hsc_batch_stats_t *out);
 

@@ -2269,6 +2269,12 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
 #pragma unroll
         for (int k = 0; k < kRec; ++k) {
             const uint32_t j = jb + k * kJoinThreads + threadIdx.x;
+            // a wave past the item's records has nothing to search or load (walk
+            // skips it the same way; the vote reads its records as empty)
+            if (__builtin_amdgcn_readfirstlane(j) >= j1) {
+                rec[k] = u32x4{0, 0, 0, 0};
+                continue;
+            }
             uint32_t g = 0;  // Es[0] = 0 <= j
 #pragma unroll
             for (int b = 8; b >= 0; --b) {

@@ -679,6 +679,8 @@ struct hsc_ctx {
     AnomOut anom_out;
     SiBufs si;               // hsc_dep_graph_si: device scratch, host results
     SiOut si_out;
+    ResolveBufs resolve;     // hsc_dep_graph_resolve: device scratch and the lowered ops, host results
+    ResolveOut resolve_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

@@ -3366,7 +3366,7 @@ int hsc_ctx_create(int device, hsc_ctx **out)
         if (!warmed[device]) {
             for (auto f : {warm_kernels, warm_ingest, warm_narrow, warm_ctiles, warm_delta,
                            warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_realtime, warm_anomaly, warm_si,
-                           warm_route})
+                           warm_resolve, warm_route})
                 (void)f();
             warmed[device] = true;
         }
@@ -3442,6 +3442,7 @@ void hsc_ctx_destroy(hsc_ctx *c)
     c->graph.release_all();
     c->anom.release_all();
     c->si.release_all();
+    c->resolve.release_all();
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -4792,6 +4793,97 @@ int hsc_dep_graph_build_device(hsc_ctx *c, size_t nops, uint32_t ntxn, const uin
     st->build_ms = build_ms;
     return graph_edge_stats(c, st);
 }
+
+int hsc_dep_graph_resolve(hsc_ctx *c, const hsc_vhistory *h, unsigned flags, hsc_resolved *out)
+{
+    if (!c || !h || !out || (h->nops && (!h->txn || !h->key || !h->is_write || !h->value)) ||
+        (h->ntxn && !h->status) || h->nops > 0x7FFFFFFFull || h->ntxn > 0x7FFFFFFFu)
+        return HSC_EINVAL;
+    if (c->host_only) return HSC_EDEVICE;
+    MuGuard g(c);
+    (void)hipSetDevice(c->device);
+    hipStream_t s = c->stream;
+    static const int dir_bits = [] {  // (A/B diagnostics: 0 = the plain binary search)
+        const char *v = getenv("HSC_RESOLVE_DIR_BITS");
+        return v ? atoi(v) : -1;
+    }();
+    hipEvent_t e0, e1;
+    HIPCHK(c, hipEventCreate(&e0));
+    HIPCHK(c, hipEventCreate(&e1));
+    ResolveOut &o = c->resolve_out;
+    const ResolveIn in{h->nops, h->ntxn, h->txn, h->key, h->is_write, h->value, h->status};
+    hipError_t e = hipEventRecord(e0, s);
+    if (e == hipSuccess) e = graph_resolve(in, c->resolve, (flags & HSC_RESOLVE_ARRAYS) != 0, dir_bits, o, s);
+    const int bad = o.bad;
+    if (e == hipSuccess) e = hipEventRecord(e1, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    memset(out, 0, sizeof *out);
+    if (e == hipSuccess) (void)hipEventElapsedTime(&out->ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (e == hipErrorInvalidValue && bad)
+        return fail(c, HSC_EINVAL,
+                    bad & 1   ? "value history: an op names a txn >= ntxn"
+                    : bad & 2 ? "value history: a write of HSC_VAL_INIT"
+                    : bad & 4 ? "value history: a status above HSC_TXN_UNKNOWN"
+                              : "value history: a written (key, value) occurs twice");
+    HIPCHK(c, e);
+    // (never a null array: an empty vector's data() may be)
+    static const uint8_t none8[1] = {0};
+    static const uint32_t none32[1] = {0};
+    static const uint64_t none64[1] = {0};
+    out->nops = h->nops;
+    out->kept_ops = o.kept_ops;
+    out->ntxn = h->ntxn;
+    out->ncommitted = o.ncommitted;
+    out->recovered = o.recovered;
+    out->aborted = o.aborted;
+    out->dropped = o.dropped;
+    out->writes = o.writes;
+    out->reads = o.reads;
+    out->g1a_reads = o.g1a_reads;
+    out->g1b_reads = o.g1b_reads;
+    out->dangling_reads = o.dangling_reads;
+    out->internal_reads = o.internal_reads;
+    out->g1a_txns = o.g1a_txns;
+    out->g1b_txns = o.g1b_txns;
+    out->fate = o.fate.empty() ? none8 : o.fate.data();
+    out->cid = o.cid.empty() ? none32 : o.cid.data();
+    out->txn_of_cid = o.txn_of_cid.empty() ? none32 : o.txn_of_cid.data();
+    out->txn_g1 = o.txn_g1.empty() ? none8 : o.txn_g1.data();
+    out->n_listed = o.n_listed;
+    out->listed_op = o.listed_op.empty() ? none64 : o.listed_op.data();
+    out->listed_wop = o.listed_wop.empty() ? none64 : o.listed_wop.data();
+    if (flags & HSC_RESOLVE_ARRAYS) {
+        out->obs_txn = o.obs_txn.empty() ? none32 : o.obs_txn.data();
+        out->obs_op = o.obs_op.empty() ? none64 : o.obs_op.data();
+        out->rflag = o.rflag.empty() ? none8 : o.rflag.data();
+    }
+    out->sweeps = o.sweeps;
+    return HSC_OK;
+}
+
+int hsc_dep_graph_build_resolved(hsc_ctx *c, int flags, hsc_graph_stats *st)
+{
+    if (!c) return HSC_EINVAL;
+    if (c->host_only) return HSC_EDEVICE;
+    MuGuard g(c);
+    (void)hipSetDevice(c->device);
+    const ResolveBufs &r = c->resolve;
+    if (!r.valid) return fail(c, HSC_ESTATE, "no resolved history (hsc_dep_graph_resolve)");
+    GraphInput in{r.l_txn.as<uint32_t>(), r.l_key.as<uint64_t>(), r.l_isw.as<uint8_t>(), r.l_obs.as<uint32_t>(),
+                  r.kept, r.nc};
+    in.skip_rw = (flags & HSC_GRAPH_NO_RW) != 0;
+    in.check = true;  // finds whether the kept ops are in txn order
+    float build_ms = 0;
+    int rc = graph_build_timed(c, in, (flags & HSC_GRAPH_FULL) != 0, &build_ms);
+    if (rc || !st) return rc;
+    memset(st, 0, sizeof *st);
+    st->build_ms = build_ms;
+    return graph_edge_stats(c, st);
+}
+
+int hsc_dep_graph_resolve_sort_path(hsc_ctx *c) { return c ? c->resolve.sort_path : 0; }
 
 int hsc_dep_graph_stage_rw_pairs(hsc_ctx *c, uint32_t nrs, const uint32_t *readset_txn,
                                  size_t ncommit, const uint64_t *commit_lsn,

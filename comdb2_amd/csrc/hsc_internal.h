@@ -715,6 +715,51 @@ struct SiOut {  // host results (hsc_si_report points into them)
 // not fit 32 bits (nothing of it was launched).  witness: one cycle per
 // flagged component.
 hipError_t graph_si(uint32_t nnodes, GraphBufs &g, SiBufs &si, bool witness, SiOut &out, hipStream_t s);
+// Version resolution (hsc_resolve.hip): a history of every
+// attempted txn with the values read and written -> the write each read
+// observed, the G1a / G1b flags, the committed set, and the committed part
+// lowered to the device-resident ops graph_build takes.  The lowered ops live
+// in buffers of their own, so a plain build between a resolve and the build of
+// its ops disturbs neither.
+struct ResolveBufs {
+    DBuf in_txn, in_key, in_isw, in_val, in_status;    // the uploaded history
+    DBuf f0, f1, scratch, words, words2, pay, pay2, gid, gid2, k0, k1;  // flags / scans, sort rows
+    DBuf fin, tab_op, tab_txn, dir;                    // final-write bits, the lookup table's payload, its key directory
+    DBuf obs_op, obs_txn, rflag;                       // per op
+    DBuf level, fate, cid, txn_of, plane, txn_g1;      // per txn
+    DBuf words_dev;                                    // error / change / count words
+    DBuf list_op, list_wop;
+    DBuf l_txn, l_key, l_isw, l_obs;                   // the lowered ops
+    size_t kept = 0;       // lowered ops
+    uint32_t nc = 0;       // their txns
+    bool valid = false;    // a resolve succeeded and its lowered ops are in place
+    int sort_path = 0;     // bit 0: the lookup table's sort ran packed, bit 1: the finality sort did
+    void release_all();
+};
+struct ResolveIn {  // host pointers
+    size_t nops;
+    uint32_t ntxn;
+    const uint32_t *txn;
+    const uint64_t *key;
+    const uint8_t *is_write;
+    const uint64_t *value;
+    const uint8_t *status;
+};
+struct ResolveOut {  // host results (hsc_resolved points into them)
+    std::vector<uint8_t> fate, txn_g1, rflag;
+    std::vector<uint32_t> cid, txn_of_cid, obs_txn;
+    std::vector<uint64_t> listed_op, listed_wop, obs_op;
+    size_t kept_ops;
+    uint32_t ncommitted, recovered, aborted, dropped, g1a_txns, g1b_txns, n_listed, sweeps;
+    uint64_t writes, reads, g1a_reads, g1b_reads, dangling_reads, internal_reads;
+    int bad;  // hipErrorInvalidValue: 1 txn >= ntxn, 2 a write of HSC_VAL_INIT, 4 a status > 2, 8 a duplicated (key, value)
+};
+// arrays: also obs_txn / obs_op / rflag to the host.  dir_bits: buckets of the
+// lookup table's key directory, as a power of two (< 0: from the row count;
+// 0: one bucket -- the plain binary search).
+hipError_t graph_resolve(const ResolveIn &in, ResolveBufs &r, bool arrays, int dir_bits,
+                         ResolveOut &out, hipStream_t s);
+hipError_t warm_resolve();
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {

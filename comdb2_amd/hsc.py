@@ -134,6 +134,33 @@ class SiReport(C.Structure):
                 ("ms", C.c_float)]
 
 
+# hsc_dep_graph_resolve: txn status, read flags, the initial value
+TXN_OK, TXN_ABORTED, TXN_UNKNOWN = 0, 1, 2
+RD_ABORTED, RD_INTERMEDIATE, RD_DANGLING, RD_INTERNAL = 1, 2, 4, 8
+VAL_INIT = 0xFFFFFFFFFFFFFFFF
+RESOLVE_ARRAYS = 1
+RESOLVE_LIST_CAP = 4096
+OBS_INIT, OBS_NONE = 0xFFFFFFFF, 0xFFFFFFFE  # hsc_resolved.obs_txn: initial version (or a write op) / no such write
+NO_OP = 0xFFFFFFFFFFFFFFFF                   # hsc_resolved.obs_op / listed_wop: no write op
+
+
+class _VHistory(C.Structure):
+    _fields_ = [("nops", C.c_size_t), ("ntxn", C.c_uint32), ("txn", _p), ("key", _p),
+                ("is_write", _p), ("value", _p), ("status", _p)]
+
+
+class Resolved(C.Structure):
+    """hsc_resolved: the arrays are host memory of the context."""
+    _fields_ = [("nops", C.c_size_t), ("kept_ops", C.c_size_t), ("ntxn", C.c_uint32),
+                ("ncommitted", C.c_uint32), ("recovered", C.c_uint32), ("aborted", C.c_uint32),
+                ("dropped", C.c_uint32), ("writes", C.c_uint64), ("reads", C.c_uint64),
+                ("g1a_reads", C.c_uint64), ("g1b_reads", C.c_uint64), ("dangling_reads", C.c_uint64),
+                ("internal_reads", C.c_uint64), ("g1a_txns", C.c_uint32), ("g1b_txns", C.c_uint32),
+                ("fate", _p), ("cid", _p), ("txn_of_cid", _p), ("txn_g1", _p), ("n_listed", C.c_uint32),
+                ("listed_op", _p), ("listed_wop", _p), ("obs_txn", _p), ("obs_op", _p), ("rflag", _p),
+                ("sweeps", C.c_uint32), ("ms", C.c_float)]
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -207,6 +234,7 @@ EXPORTS = [
     "hsc_small_stats", "hsc_harness_concurrent",
     "hsc_dep_graph_build", "hsc_dep_graph_stage_rw_pairs", "hsc_dep_graph_stage_realtime", "hsc_dep_graph_scc_built", "hsc_dep_graph_build_device", "hsc_dep_graph_cover", "hsc_dep_graph_cut", "hsc_dep_graph_scc_cut",
     "hsc_dep_graph_anomalies", "hsc_dep_graph_si",
+    "hsc_dep_graph_resolve", "hsc_dep_graph_build_resolved", "hsc_dep_graph_resolve_sort_path",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -296,6 +324,9 @@ def load() -> C.CDLL:
         "hsc_dep_graph_cut": (C.c_int, [_p, _p, _p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "hsc_dep_graph_anomalies": (C.c_int, [_p, C.c_uint, C.c_uint, C.POINTER(Anomalies)]),
         "hsc_dep_graph_si": (C.c_int, [_p, C.c_uint, C.POINTER(SiReport)]),
+        "hsc_dep_graph_resolve": (C.c_int, [_p, C.POINTER(_VHistory), C.c_uint, C.POINTER(Resolved)]),
+        "hsc_dep_graph_build_resolved": (C.c_int, [_p, C.c_int, C.POINTER(GraphStats)]),
+        "hsc_dep_graph_resolve_sort_path": (C.c_int, [_p]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
         "hsc_window_ingest_raw": (C.c_int, [_p, C.POINTER(_RawLog)]),
@@ -1134,8 +1165,9 @@ class Validator:
         flagged component (wit_off, wit_txn, wit_type; empty without witness)
         and the stats.  No flagged component: the history's dependency graph
         is allowed under snapshot isolation (strong snapshot isolation when
-        the real-time order was staged); aborted and intermediate reads are
-        not modelled.  The arrays are copies."""
+        the real-time order was staged).  Aborted and intermediate reads
+        (G1a / G1b) are not this call's: dep_graph_resolve reports them for a
+        history given with its values.  The arrays are copies."""
         a = SiReport()
         self._chk(self.lib.hsc_dep_graph_si(self.ctx, SI_WITNESS if witness else 0, C.byref(a)),
                   "hsc_dep_graph_si")
@@ -1156,6 +1188,58 @@ class Validator:
                   "scc_iterations", "bfs_levels", "ms"):
             out[k] = getattr(a, k)
         return out
+
+    def dep_graph_resolve(self, vh, arrays: bool = True) -> dict:
+        """Version resolution of a value history (workloads.ValueHistory;
+        hsc_dep_graph_resolve): which write each read observed, the aborted /
+        intermediate / dangling / internal read flags, which UNKNOWN txns
+        committed, and the committed part lowered on the device for
+        dep_graph_build_resolved.  Copies of every field; without ``arrays``
+        the per-op obs_txn / obs_op / rflag are None.  ``sort_path``: bit 0 the
+        lookup table's sort ran packed, bit 1 the finality sort did."""
+        cols = [np.ascontiguousarray(vh.txn, np.uint32), np.ascontiguousarray(vh.key, np.uint64),
+                np.ascontiguousarray(vh.is_write, np.uint8), np.ascontiguousarray(vh.value, np.uint64),
+                np.ascontiguousarray(vh.status, np.uint8)]
+        n, ntxn = len(cols[0]), int(vh.ntxn)
+        if not (len(cols[1]) == len(cols[2]) == len(cols[3]) == n) or len(cols[4]) != ntxn:
+            raise ValueError("value history: the per-op arrays must share a length and status must hold ntxn")
+        hs = _VHistory(n, ntxn, *[c.ctypes.data for c in cols])
+        a = Resolved()
+        self._chk(self.lib.hsc_dep_graph_resolve(self.ctx, C.byref(hs), RESOLVE_ARRAYS if arrays else 0,
+                                                 C.byref(a)), "hsc_dep_graph_resolve")
+
+        def arr(p, n, dt):
+            if n == 0:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)),
+                                         shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+
+        out = {k: getattr(a, k) for k in ("nops", "kept_ops", "ntxn", "ncommitted", "recovered", "aborted",
+                                          "dropped", "writes", "reads", "g1a_reads", "g1b_reads",
+                                          "dangling_reads", "internal_reads", "g1a_txns", "g1b_txns",
+                                          "n_listed", "sweeps", "ms")}
+        out["fate"] = arr(a.fate, ntxn, np.uint8)
+        out["cid"] = arr(a.cid, ntxn, np.uint32)
+        out["txn_of_cid"] = arr(a.txn_of_cid, a.ncommitted, np.uint32)
+        out["txn_g1"] = arr(a.txn_g1, ntxn, np.uint8)
+        out["listed_op"] = arr(a.listed_op, a.n_listed, np.uint64)
+        out["listed_wop"] = arr(a.listed_wop, a.n_listed, np.uint64)
+        for k, dt in (("obs_txn", np.uint32), ("obs_op", np.uint64), ("rflag", np.uint8)):
+            out[k] = arr(getattr(a, k), n, dt) if arrays else None
+            if not arrays and getattr(a, k):
+                raise HscError(f"hsc_dep_graph_resolve: {k} set without HSC_RESOLVE_ARRAYS")
+        out["sort_path"] = int(self.lib.hsc_dep_graph_resolve_sort_path(self.ctx))
+        return out
+
+    def dep_graph_build_resolved(self, full: bool = True, no_rw: bool = False) -> dict:
+        """dep_graph_build over the lowered ops of the last dep_graph_resolve
+        (its ncommitted txns, ids = cid): joins staged rw pairs / real-time
+        edges like any build (hsc_dep_graph_build_resolved)."""
+        st = GraphStats()
+        flags = (1 if full else 0) | (2 if no_rw else 0)
+        self._chk(self.lib.hsc_dep_graph_build_resolved(self.ctx, flags, C.byref(st)),
+                  "hsc_dep_graph_build_resolved")
+        return st.as_dict()
 
     def probe_device(self, batch: ProbeBatch) -> None:
         self._chk(self.lib.hsc_probe_device(self.ctx, C.byref(batch)), "hsc_probe_device")

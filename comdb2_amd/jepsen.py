@@ -48,8 +48,21 @@ edges the G2 checker looks for).
 serializable is at least snapshot isolation (comdb2 ships that level as
 ``enable_snapshot_isolation``; adya.clj's write skew is legal under it).  That
 verdict is the dependency-graph condition only -- every cycle has two adjacent
-anti-dependency edges -- over the committed txns: ``:fail`` ops are dropped by
-the conversion, so aborted and intermediate reads (G1a, G1b) are not modelled.
+anti-dependency edges -- over the committed txns: the register / insert
+conversion above drops ``:fail`` ops and resolves reads to writer txns, so
+``check_edn`` does not model aborted and intermediate reads (G1a, G1b).
+
+The value entry does.  :func:`vhistory_from_txn_edn` reads multi-op txn
+histories (``:f :txn :value [[:r k v] [:w k v] ...]``, Elle's rw-register
+form) into a :class:`workloads.ValueHistory` of every attempted txn -- ``:ok``,
+``:fail`` (aborted) and ``:info`` / unpaired (unknown) alike -- and
+:func:`check_txn_edn` has the GPU find the write each read observed
+(``Validator.dep_graph_resolve``), report G1a / G1b, decide which unknown txns
+committed, and run the analyses of ``check_edn`` on the committed part.
+:func:`check_dirty_reads_edn` does the resolve alone for the reference's
+dirty-reads workload (linearizable/jepsen/src/comdb2/core.clj:320-353,
+:492-523: "a failed transaction whose value became visible to some read").
+Internal consistency (a txn reading its own earlier write) is not checked.
 """
 from __future__ import annotations
 
@@ -59,7 +72,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .workloads import History
+from .workloads import TXN_ABORTED, TXN_OK, TXN_UNKNOWN, VAL_INIT, History, ValueHistory
 
 # ---------------------------------------------------------------------------
 # EDN (the subset the histories use: maps, vectors, keywords, integers, nil,
@@ -366,7 +379,8 @@ def isolation_report(ops: JepsenOps, result: dict, si: dict, strict: Optional[di
     ``snapshot_isolation``, ``serializable``, with ``strict``
     ``strict_serializable`` and with ``strict_si`` too
     ``strong_snapshot_isolation``.  All of it is the dependency-graph
-    condition over committed txns: G1a / G1b are not modelled."""
+    condition over committed txns: G1a / G1b are :func:`check_txn_edn`'s
+    (``levels["read_committed"]``), not this function's."""
     labels = [int(x) for x in si.get("comp_label", ())]
     flagged = [int(x) for x in si.get("comp_nonadj", ())]
     plain = {int(l): int(k) for l, k in zip(result.get("comp_label", ()), result.get("comp_class", ()))}
@@ -419,9 +433,17 @@ def check_edn(validator, text: str, witness: bool = True, realtime: bool = False
     ``si_analysis`` (dep_graph_si's dict).  With ``realtime`` as well the
     analysis runs again on the real-time build and ``levels`` has
     ``strong_snapshot_isolation``.  Aborted and intermediate
-    reads are not modelled (the module docstring)."""
+    reads are not modelled by this conversion (the module docstring;
+    :func:`check_txn_edn` models them)."""
     ops = history_from_jepsen_edn(text)
-    validator.dep_graph_build(ops.history, full=True)
+    return _check_built(validator, ops, lambda: validator.dep_graph_build(ops.history, full=True),
+                        ops.history.ntxn, witness, realtime, isolation)
+
+
+def _check_built(validator, ops, build, ntxn: int, witness: bool, realtime: bool, isolation: bool) -> dict:
+    """check_edn from the build on: ``build()`` builds the full graph of the
+    ntxn txns whose completions and intervals ``ops`` holds."""
+    build()
     result = validator.dep_graph_anomalies(witness=witness)
     report = anomaly_report(ops, result)
     report["history"] = ops
@@ -433,9 +455,9 @@ def check_edn(validator, text: str, witness: bool = True, realtime: bool = False
             report["si_analysis"] = si
         return report
     staged = validator.dep_graph_stage_realtime(ops.invoke, ops.complete)
-    validator.dep_graph_build(ops.history, full=True)
+    build()
     strict = dict(validator.dep_graph_anomalies(witness=witness))
-    scc, _ = validator.dep_graph_scc_built(ops.history.ntxn)
+    scc, _ = validator.dep_graph_scc_built(ntxn)
     strict["edges"], strict["stage_ms"] = staged["edges"], staged["ms"]
     plain_cls = np.asarray(result["cls"])
     cycles = []
@@ -451,6 +473,240 @@ def check_edn(validator, text: str, witness: bool = True, realtime: bool = False
         report.update(isolation_report(ops, result, si, strict, strict_si))
         report["si_analysis"] = si
     return report
+
+
+# ---------------------------------------------------------------------------
+# value histories: every attempted txn, reads resolved on the GPU
+# ---------------------------------------------------------------------------
+@dataclasses.dataclass
+class TxnOps:
+    """Every attempted txn of a history, in txn id order."""
+    vhistory: ValueHistory
+    ok: int                  # :ok completions (TXN_OK)
+    failed: int              # :fail completions (TXN_ABORTED)
+    info: int                # :info completions (TXN_UNKNOWN)
+    unpaired: int            # invokes without a completion (TXN_UNKNOWN)
+    txn_ops: List[dict]      # the completion of each txn (an unpaired txn's invoke)
+    # each txn's interval (JepsenOps.invoke / .complete): an :ok or :fail op's
+    # is [its invoke, its completion], any other's [its invoke, RT_OPEN]
+    invoke: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint64))
+    complete: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint64))
+    g2_keys: Dict[int, int] = dataclasses.field(default_factory=dict)  # (anomaly_report reads it: none here)
+
+
+def _attempts(text: str, fs) -> List[tuple]:
+    """Every op whose :f is in fs as an attempted txn, in txn id order:
+    (invoke or {}, completion or None, status, line of the invoke or -1, line
+    of the completion or -1).  Ids run in order of (completion time for :ok /
+    :fail, invoke time for the others, then line), as history_from_jepsen_edn
+    orders its candidates."""
+    pending: Dict[object, Tuple[dict, int]] = {}
+    rows = []
+    for i, op in enumerate(_flatten(parse_edn(text))):
+        if not isinstance(op, dict):
+            continue
+        t, p = op.get(":type"), op.get(":process")
+        if t == ":invoke":
+            pending[p] = (op, i)
+        elif t in (":ok", ":fail", ":info"):
+            inv, il = pending.pop(p, (None, -1))
+            if op.get(":f", (inv or {}).get(":f")) not in fs:
+                continue
+            if t == ":info":
+                rows.append((_time(inv, il) if inv else i, il if inv else i, inv or {}, op, TXN_UNKNOWN, il, i))
+            else:
+                rows.append((_time(op, i), i, inv or {}, op, TXN_OK if t == ":ok" else TXN_ABORTED, il, i))
+    for inv, il in pending.values():
+        if inv.get(":f") in fs:
+            rows.append((_time(inv, il), il, inv, None, TXN_UNKNOWN, il, -1))
+    rows.sort(key=lambda r: (r[0], r[1]))
+    return [r[2:] for r in rows]
+
+
+def _attempt_intervals(att) -> Tuple[np.ndarray, np.ndarray]:
+    seen = [o for inv, op, _, il, cl in att for o in ((inv,) if il >= 0 else ()) + ((op,) if op is not None else ())]
+    use_time = all(type(o.get(":time")) is int for o in seen)
+    rows = []
+    for inv, op, st, il, cl in att:
+        end = None if op is None else (op[":time"] if use_time else cl)
+        start = end if il < 0 else (inv[":time"] if use_time else il)
+        rows.append((start if end is None else min(start, end), end if st != TXN_UNKNOWN else None))
+    base = min([0] + [r[0] for r in rows])
+    return (np.array([a - base for a, _ in rows], np.uint64),
+            np.array([RT_OPEN if b is None else b - base for _, b in rows], np.uint64))
+
+
+def _txn_ops_record(att, txn, key, isw, val) -> TxnOps:
+    status = np.array([a[2] for a in att], np.uint8)
+    vh = ValueHistory(np.array(txn, np.uint32), np.array(key, np.uint64), np.array(isw, np.uint8),
+                      np.array(val, np.uint64), status, len(att))
+    invoke, complete = _attempt_intervals(att)
+    return TxnOps(vh, int((status == TXN_OK).sum()), int((status == TXN_ABORTED).sum()),
+                  sum(1 for a in att if a[2] == TXN_UNKNOWN and a[1] is not None),
+                  sum(1 for a in att if a[1] is None), [a[1] if a[1] is not None else a[0] for a in att],
+                  invoke, complete)
+
+
+def vhistory_from_txn_edn(text: str) -> TxnOps:
+    """Multi-op txn histories, ``{:f :txn :value [[:r k v] [:w k v] ...]}``
+    (keys and values non-negative integers), as a value history of every
+    attempted txn: a paired or unpaired op is a txn -- ``:ok`` is TXN_OK,
+    ``:fail`` TXN_ABORTED, ``:info`` or an invoke without a completion
+    TXN_UNKNOWN.  A ``nil`` read of an ``:ok`` op saw the initial state
+    (VAL_INIT); the micro-ops of any other op come from its invoke, whose
+    reads are ``nil`` and are left out."""
+    att = _attempts(text, (":txn",))
+    txn, key, isw, val = [], [], [], []
+    for t, (inv, op, st, _, _) in enumerate(att):
+        src = op if st == TXN_OK else (inv if ":value" in inv else (op or {}))
+        for m in src.get(":value") or ():
+            f, k, v = m
+            if f == ":w":
+                if v is None:
+                    raise ValueError("a :w micro-op without a value")
+                txn.append(t), key.append(int(k)), isw.append(1), val.append(int(v))
+            elif f == ":r":
+                if st != TXN_OK:
+                    continue
+                txn.append(t), key.append(int(k)), isw.append(0), val.append(VAL_INIT if v is None else int(v))
+            else:
+                raise ValueError(f"unknown micro-op {f!r}")
+    return _txn_ops_record(att, txn, key, isw, val)
+
+
+_RESOLVE_STATS = ("nops", "kept_ops", "ntxn", "ncommitted", "recovered", "aborted", "dropped", "writes", "reads",
+                  "g1a_reads", "g1b_reads", "dangling_reads", "internal_reads", "g1a_txns", "g1b_txns",
+                  "n_listed", "sweeps", "ms")
+_RD_ABORTED, _RD_INTERMEDIATE, _RD_DANGLING = 1, 2, 4  # HSC_RD_*
+
+
+def listed_reads(vh: ValueHistory, res: dict) -> dict:
+    """``aborted_reads`` / ``intermediate_reads`` / ``dangling_reads`` of a
+    dep_graph_resolve(arrays=True) dict: one entry {reader, writer, key,
+    value, reader_op, writer_op} per listed read carrying the flag (writer
+    and writer_op None for a dangling read), and the exact ``*_count`` of each
+    (the lists stop at the entry's cap)."""
+    out = {"aborted_reads": [], "intermediate_reads": [], "dangling_reads": []}
+    for i, j in zip(res["listed_op"], res["listed_wop"]):
+        i, j = int(i), int(j)
+        none = j == 0xFFFFFFFFFFFFFFFF
+        e = {"reader": int(vh.txn[i]), "writer": None if none else int(vh.txn[j]), "key": int(vh.key[i]),
+             "value": int(vh.value[i]), "reader_op": i, "writer_op": None if none else j}
+        f = int(res["rflag"][i])
+        for bit, name in ((_RD_ABORTED, "aborted_reads"), (_RD_INTERMEDIATE, "intermediate_reads"),
+                          (_RD_DANGLING, "dangling_reads")):
+            if f & bit:
+                out[name].append(e)
+    out["aborted_read_count"] = int(res["g1a_reads"])
+    out["intermediate_read_count"] = int(res["g1b_reads"])
+    out["dangling_read_count"] = int(res["dangling_reads"])
+    return out
+
+
+def check_txn_edn(validator, text: str, witness: bool = True, realtime: bool = False,
+                  isolation: bool = False) -> dict:
+    """A multi-op txn history through the GPU by value: resolve every read to
+    the write it observed (``Validator.dep_graph_resolve``), build the graph
+    of the committed part (``dep_graph_build_resolved``) and run exactly the
+    analyses of :func:`check_edn`.  The report has check_edn's keys -- the txns
+    of ``cycles`` / ``si_cycles`` / ``realtime_cycles`` and their ``label``
+    are attempted-txn ids (``history.txn_ops``), while ``analysis`` and its
+    kin stay in committed ids, ``resolve_arrays["txn_of_cid"]`` mapping them
+    -- plus :func:`listed_reads`' keys; ``anomaly_types`` gains "G1a" /
+    "G1b"; ``valid`` = no cycle, no G1a and no G1b; ``levels`` (with
+    ``isolation``) gains ``read_committed`` = no G1a, no G1b and
+    ``g1c_free``; ``resolve`` holds the entry's stats, ``history`` the
+    :class:`TxnOps`.  With ``realtime`` the intervals of the committed txns
+    are staged; a recovered txn is open.  Internal consistency is not
+    checked."""
+    tx = vhistory_from_txn_edn(text)
+    res = validator.dep_graph_resolve(tx.vhistory, arrays=True)
+    toc = [int(t) for t in res["txn_of_cid"]]
+    sel = np.asarray(toc, np.int64)
+    committed = TxnOps(tx.vhistory, tx.ok, tx.failed, tx.info, tx.unpaired, [tx.txn_ops[t] for t in toc],
+                       tx.invoke[sel], tx.complete[sel])
+    report = _check_built(validator, committed, lambda: validator.dep_graph_build_resolved(full=True),
+                          len(toc), witness, realtime, isolation)
+    for name in ("cycles", "si_cycles", "realtime_cycles"):
+        for c in report.get(name, ()):
+            c["txns"] = [toc[t] for t in c["txns"]]
+            c["label"] = toc[c["label"]]
+    report["history"] = tx
+    report.update(listed_reads(tx.vhistory, res))
+    g1a, g1b = int(res["g1a_reads"]) > 0, int(res["g1b_reads"]) > 0
+    report["anomaly_types"] = sorted(set(report["anomaly_types"]) | ({"G1a"} if g1a else set())
+                                     | ({"G1b"} if g1b else set()))
+    report["valid"] = bool(report["valid"]) and not g1a and not g1b
+    if isolation:
+        report["levels"]["read_committed"] = not g1a and not g1b and bool(report["levels"]["g1c_free"])
+    report["resolve"] = {k: res[k] for k in _RESOLVE_STATS if k in res}
+    report["resolve_arrays"] = {k: res[k] for k in ("fate", "cid", "txn_of_cid", "txn_g1")}
+    return report
+
+
+# ---- the reference's dirty-reads workload (core.clj:320-353, :492-523) ------
+@dataclasses.dataclass
+class DirtyOps:
+    ops: TxnOps
+    n: int              # rows
+    short_reads: int    # :ok reads of fewer than n values (their positions are lost)
+    reads: List[int]    # the txn ids of the :ok reads
+
+
+def dirty_reads_from_edn(text: str, n: Optional[int] = None) -> DirtyOps:
+    """The dirty-reads workload as a value history: ``:f :write :value x``
+    writes x to rows 0 .. n - 1 in one txn; ``:f :read`` returns the x of
+    every row that is not still initial, without row ids.  n defaults to the
+    longest read (at least 1).  A read of n values maps position to key; a
+    shorter one has lost its positions, and its values get keys 0 .. len - 1
+    -- every write covers every row, so the (key, value) lookup, and with it
+    G1a, stays exact while those keys mean nothing.  That is why this history
+    is for the resolve alone, never for a graph."""
+    att = _attempts(text, (":read", ":write"))
+    f_of = [(op or inv).get(":f", inv.get(":f")) for inv, op, _, _, _ in att]
+    vals_of = [list(op.get(":value") or ()) if f == ":read" and st == TXN_OK else None
+               for f, (inv, op, st, _, _) in zip(f_of, att)]
+    if n is None:
+        n = max([1] + [len(v) for v in vals_of if v is not None])
+    txn, key, isw, val, reads, short = [], [], [], [], [], 0
+    for t, (f, (inv, op, st, _, _)) in enumerate(zip(f_of, att)):
+        if f == ":write":
+            x = inv.get(":value", (op or {}).get(":value"))
+            for k in range(n):
+                txn.append(t), key.append(k), isw.append(1), val.append(int(x))
+        elif vals_of[t] is not None:
+            vs = vals_of[t]
+            if len(vs) > n:
+                raise ValueError("a read of more values than rows")
+            reads.append(t)
+            short += len(vs) < n
+            for k, x in enumerate(vs):
+                txn.append(t), key.append(k), isw.append(0), val.append(int(x))
+    return DirtyOps(_txn_ops_record(att, txn, key, isw, val), n, short, reads)
+
+
+def dirty_reads_report(d: DirtyOps, res: dict) -> dict:
+    """The dirty-reads checker's answer from a dep_graph_resolve dict (a pure
+    function of its arguments): ``dirty_reads`` -- the values of the :ok reads
+    holding a value of a :fail write, in txn order (the checker's docstring:
+    "a failed transaction whose value became visible to some read");
+    ``dirty_read_txns`` their txn ids; ``inconsistent_reads`` -- the reads
+    whose values are not all equal (computed here, on the host); ``valid`` --
+    no dirty read; ``short_reads``; ``resolve`` the entry's stats."""
+    g1 = res["txn_g1"]
+    dirty = [t for t in d.reads if int(g1[t]) & 1]
+    values = {t: list(d.ops.txn_ops[t].get(":value") or ()) for t in d.reads}
+    return {"valid": not dirty, "dirty_reads": [values[t] for t in dirty], "dirty_read_txns": dirty,
+            "inconsistent_reads": [values[t] for t in d.reads if len(set(values[t])) > 1],
+            "short_reads": d.short_reads, "n": d.n, "history": d,
+            "resolve": {k: res[k] for k in _RESOLVE_STATS if k in res}}
+
+
+def check_dirty_reads_edn(validator, text: str, n: Optional[int] = None) -> dict:
+    """The reference's dirty-reads checker through the GPU: the resolve only
+    (no graph: :func:`dirty_reads_from_edn`), then :func:`dirty_reads_report`."""
+    d = dirty_reads_from_edn(text, n)
+    return dirty_reads_report(d, validator.dep_graph_resolve(d.ops.vhistory, arrays=False))
 
 
 # ---------------------------------------------------------------------------
@@ -542,3 +798,106 @@ def adya_g2_edn(seed: int, n_keys: int = 500, anomaly: float = 0.05) -> Tuple[st
             bad.append(k)
         t += 10
     return "\n".join(lines) + "\n", bad
+
+
+def txn_history_edn(seed: int, n_txns: int = 2000, n_procs: int = 8, n_keys: int = 50, fail: float = 0.05,
+                    info: float = 0.03, dirty: float = 0.02, intermediate: float = 0.02) -> Tuple[str, dict]:
+    """A multi-op txn history (``:f :txn``) of a serial execution with
+    injected anomalies: ``fail`` of the txns complete :fail (their writes are
+    not applied), ``info`` complete :info or never (applied half the time);
+    a read returns with probability ``dirty`` a value a failed txn wrote and
+    with probability ``intermediate`` a value its writer overwrote itself.
+    Written values are unique.  Returns (EDN text, {"g1a": injected dirty
+    reads of :ok txns, "g1b": injected intermediate reads of :ok txns})."""
+    rng = np.random.default_rng(seed)
+    latest: Dict[int, int] = {}
+    dead: List[Tuple[int, int]] = []
+    stale: List[Tuple[int, int]] = []
+    lines: List[Tuple[int, int, str]] = []
+    busy = np.zeros(n_procs, np.int64)
+    now, nextv, inj = 1000, 1, {"g1a": 0, "g1b": 0}
+
+    def fmt(ms, blank):
+        return "[" + " ".join(f"[{f} {k} {'nil' if v is None or (blank and f == ':r') else v}]" for f, k, v in ms) + "]"
+
+    for _ in range(n_txns):
+        now += int(rng.integers(1, 50))
+        p = int(rng.integers(0, n_procs))
+        inv_t = max(int(busy[p]) + 1, now - int(rng.integers(0, 400)))
+        u = rng.random()
+        kind = ":fail" if u < fail else ":info" if u < fail + info else ":ok"
+        applied = kind == ":ok" or (kind == ":info" and rng.random() < 0.5)
+        ms, mine, a, b = [], {}, 0, 0
+        for _ in range(int(rng.integers(1, 5))):
+            k = int(rng.integers(0, n_keys))
+            if rng.random() < 0.5:
+                for q in range(2 if rng.random() < 0.15 else 1):
+                    if k in mine:
+                        stale.append((k, mine[k]))
+                    mine[k] = nextv
+                    ms.append((":w", k, nextv))
+                    nextv += 1
+            else:
+                r = rng.random()
+                if r < dirty and dead:
+                    k, v = dead[int(rng.integers(0, len(dead)))]
+                    a += 1
+                elif r < dirty + intermediate and stale:
+                    k, v = stale[int(rng.integers(0, len(stale)))]
+                    b += 1
+                else:
+                    v = mine.get(k, latest.get(k))
+                ms.append((":r", k, v))
+        if applied:
+            latest.update(mine)
+        elif kind == ":fail":
+            dead.extend(mine.items())
+        if kind == ":ok":
+            inj["g1a"] += a
+            inj["g1b"] += b
+        lines.append((inv_t, len(lines), f"{{:type :invoke :f :txn :value {fmt(ms, True)} :process {p} :time {inv_t}}}"))
+        if kind != ":info" or rng.random() < 0.5:  # (the rest never complete)
+            lines.append((now, len(lines), f"{{:type {kind} :f :txn :value {fmt(ms, kind != ':ok')} :process {p} "
+                                           f":time {now}}}"))
+            busy[p] = now
+        else:
+            busy[p] = now
+            p_new = n_procs + len(lines)  # a crashed process never comes back
+            lines[-1] = (inv_t, lines[-1][1], lines[-1][2].replace(f":process {p} ", f":process {p_new} "))
+    lines.sort()
+    return "\n".join(l for _, _, l in lines) + "\n", inj
+
+
+def dirty_reads_edn(seed: int, n_ops: int = 600, n_rows: int = 4, fail: float = 0.2,
+                    dirty: float = 0.05) -> Tuple[str, List[List[int]]]:
+    """The dirty-reads workload's history (core.clj:320-353) of a serial
+    execution: writes of a fresh x to every row, ``fail`` of them :fail;
+    reads return the rows' x (nothing before the first write: a short, empty
+    read; sometimes a short read of a prefix).  With probability ``dirty`` a
+    read shows a failed write's x in one row.  Returns (EDN text, the values
+    of the dirty reads in order)."""
+    rng = np.random.default_rng(seed)
+    lines, injected, dead = [], [], []
+    cur, x, t = None, 0, 1000
+    for _ in range(n_ops):
+        p = int(rng.integers(0, 5))
+        t += 10
+        if rng.random() < 0.5:
+            x += 1
+            ok = rng.random() >= fail
+            lines.append(f"{{:type :invoke :f :write :value {x} :process {p} :time {t}}}")
+            lines.append(f"{{:type {':ok' if ok else ':fail'} :f :write :value {x} :process {p} :time {t + 5}}}")
+            if ok:
+                cur = x
+            else:
+                dead.append(x)
+        else:
+            vals = [] if cur is None else [cur] * n_rows
+            if vals and rng.random() < 0.2:
+                vals = vals[: int(rng.integers(1, n_rows))]  # a short read
+            if vals and dead and rng.random() < dirty:
+                vals[int(rng.integers(0, len(vals)))] = dead[int(rng.integers(0, len(dead)))]
+                injected.append(list(vals))
+            lines.append(f"{{:type :invoke :f :read :value nil :process {p} :time {t}}}")
+            lines.append(f"{{:type :ok :f :read :value [{' '.join(map(str, vals))}] :process {p} :time {t + 5}}}")
+    return "\n".join(lines) + "\n", injected

@@ -483,6 +483,55 @@ class History:
         return int(len(self.txn))
 
 
+VAL_INIT = 0xFFFFFFFFFFFFFFFF  # HSC_VAL_INIT: a read of the initial state
+TXN_OK, TXN_ABORTED, TXN_UNKNOWN = 0, 1, 2
+
+
+@dataclasses.dataclass
+class ValueHistory:
+    """Micro-ops of every attempted transaction, by value (hsc_vhistory): a
+    write carries the value written, a read the value returned (VAL_INIT: the
+    initial state).  The ops of one txn stand in program order; the txns that
+    count as committed, in ascending id, are in commit order; written
+    (key, value) pairs are unique."""
+    txn: np.ndarray        # uint32[nops]
+    key: np.ndarray        # uint64[nops]
+    is_write: np.ndarray   # uint8[nops]
+    value: np.ndarray      # uint64[nops]
+    status: np.ndarray     # uint8[ntxn] TXN_OK / TXN_ABORTED / TXN_UNKNOWN
+    ntxn: int
+
+    @property
+    def nops(self) -> int:
+        return int(len(self.txn))
+
+
+def value_history(h: History, status: Optional[np.ndarray] = None) -> ValueHistory:
+    """h in value form: a write's value is its txn + 1, a read's the observed
+    txn + 1 (VAL_INIT for the initial version).  Every txn OK unless status
+    says otherwise.  A txn's second and later writes of one key are left out
+    (they would repeat a written (key, value); the build takes them as one
+    version anyway)."""
+    isw = np.asarray(h.is_write, np.uint8)
+    w = np.nonzero(isw)[0]
+    if len(w):
+        o = np.lexsort((w, np.asarray(h.txn)[w], np.asarray(h.key)[w]))
+        k, t = np.asarray(h.key)[w][o], np.asarray(h.txn)[w][o]
+        rep = np.zeros(len(w), bool)
+        rep[1:] = (k[1:] == k[:-1]) & (t[1:] == t[:-1])
+        if rep.any():
+            keep = np.ones(len(isw), bool)
+            keep[w[o][rep]] = False
+            h = History(np.asarray(h.txn)[keep], np.asarray(h.key)[keep], isw[keep],
+                        np.asarray(h.observed)[keep], h.ntxn)
+            isw = h.is_write
+    obs = np.asarray(h.observed, np.int64)
+    val = np.where(isw != 0, np.asarray(h.txn, np.uint64) + np.uint64(1),
+                   np.where(obs < 0, np.uint64(VAL_INIT), (obs + 1).astype(np.uint64))).astype(np.uint64)
+    st = np.zeros(h.ntxn, np.uint8) if status is None else np.asarray(status, np.uint8)
+    return ValueHistory(np.asarray(h.txn, np.uint32), np.asarray(h.key, np.uint64), isw, val, st, h.ntxn)
+
+
 def config4_history(seed: int = SEED_CONFIG4, n_txn: int = 1_000_000, n_keys: int = 100_000,
                     ops_per_txn: int = 4, write_frac: float = 0.5, concurrent_frac: float = 0.02,
                     max_lag: int = 64, zipf: float = 0.0) -> History:

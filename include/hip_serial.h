@@ -905,8 +905,9 @@ int hsc_dep_graph_anomalies(hsc_ctx *ctx, unsigned flags, unsigned max_anti_batc
  * skew only).  The answer is exact whatever max_anti_batches was given to
  * hsc_dep_graph_anomalies: no reach budget enters here.
  * Scope: this is the dependency-graph condition only.  The graph is built
- * from committed txns; aborted and intermediate reads (G1a, G1b) are not
- * modelled.  With a staged real-time order the definitions hold unchanged
+ * from committed txns: aborted and intermediate reads (G1a, G1b) are reported
+ * by hsc_dep_graph_resolve (below) for a history given with its values, not by
+ * this call; internal consistency is not checked anywhere.  With a staged real-time order the definitions hold unchanged
  * over the widened E1, and the verdict is strong snapshot isolation.
  * HSC_SI_WITNESS: per flagged component one simple cycle of >= 2 of its txns,
  * wit_txn[wit_off[i], wit_off[i + 1]), every step an edge of the build with
@@ -935,6 +936,96 @@ typedef struct hsc_si_report {
     float ms;                                     /* device time, both SCC runs included */
 } hsc_si_report;
 int hsc_dep_graph_si(hsc_ctx *ctx, unsigned flags, hsc_si_report *out);
+/* ---- version resolution: aborted and intermediate reads (G1a, G1b) ---------
+ * The graph entries above take committed txns whose reads already name the
+ * writer they observed.  This entry takes the history of every attempted txn
+ * with the values it read and wrote, finds on the GPU the write each read
+ * observed, flags aborted (G1a) and intermediate (G1b) reads, decides which
+ * indeterminate txns committed, and lowers the committed part to the
+ * device-resident ops hsc_dep_graph_build_device takes, so that every analysis
+ * above runs unchanged on a history that came from values.
+ * Premises:
+ *   - the ops of one txn stand in program order in the arrays (they need not
+ *     be contiguous);
+ *   - the txns that count as committed (the set C below), taken in ascending
+ *     id, are in commit order -- the rule of hsc_history;
+ *   - written (key, value) pairs are unique over the whole history, aborted and
+ *     unknown txns included (Elle's rw-register premise); the same value on
+ *     two keys is fine.
+ * Resolution.  Read op i of txn r has key k and value v.  v == HSC_VAL_INIT:
+ * it observed the initial version, no flags.  Otherwise it observed the write
+ * op j with key[j] == k && value[j] == v; no such j: HSC_RD_DANGLING.  With
+ * w = txn[j]: w == r gives HSC_RD_INTERNAL and no other flag; otherwise
+ * status[w] == HSC_TXN_ABORTED gives HSC_RD_ABORTED, and j not being the last
+ * write of k by w in program order gives HSC_RD_INTERMEDIATE (both may be
+ * set).  Flags are computed for every read, whatever the reader's status.
+ * Committed set C: the least set that holds every OK txn and every UNKNOWN txn
+ * one of whose writes is observed (w != r) by a read of a txn in C.  An UNKNOWN
+ * txn in C is recovered, one outside C dropped; an ABORTED txn is never in C.
+ * Anomalies: only reads of txns in C count.  G1a: a read with HSC_RD_ABORTED;
+ * G1b: a read with HSC_RD_INTERMEDIATE; txn_g1[r] bit 1 / bit 2: r is in C and
+ * has such a read.
+ * Internal consistency (a txn that reads k after writing k must see its own
+ * last write) is NOT checked: an internal read is only counted.
+ * Lowering: cid[t] = the dense rank of t among C in ascending id, 0xFFFFFFFF
+ * outside C; txn_of_cid its inverse.  The kept ops, in array order, are all
+ * ops of txns in C except reads flagged DANGLING or ABORTED; a kept op has
+ * txn := cid[txn], a kept read observed := cid[w] (0xFFFFFFFF: the initial
+ * version).  Intermediate and internal reads are kept (their wr edge is real;
+ * the build drops self edges).  Several writes of one key by one txn are one
+ * version (the build dedupes (key, txn)).
+ * writes / reads count every op of the history; the g1a / g1b / dangling /
+ * internal counts the reads of txns in C.
+ * HSC_EINVAL: a NULL argument, txn[i] >= ntxn, a status above 2, a write of
+ * HSC_VAL_INIT, a duplicated written (key, value), more than 2^31 - 1 ops or
+ * txns.  HSC_EDEVICE: a host-only context.  nops == 0 and ntxn == 0 succeed.
+ * The arrays are host memory owned by the context, never NULL except the three
+ * per-op ones without HSC_RESOLVE_ARRAYS, valid until the next graph call.
+ * The lowered ops stay on the device in buffers of their own: a plain
+ * hsc_dep_graph_build does not disturb them, nor they it.  The sharded path
+ * (hsc_multi_graph_scc) has no such entry. */
+#define HSC_VAL_INIT     UINT64_MAX   /* a read that saw the initial state; not a legal written value */
+#define HSC_TXN_OK       0
+#define HSC_TXN_ABORTED  1
+#define HSC_TXN_UNKNOWN  2            /* :info / crashed: may have committed */
+#define HSC_RD_ABORTED      1
+#define HSC_RD_INTERMEDIATE 2
+#define HSC_RD_DANGLING     4
+#define HSC_RD_INTERNAL     8
+typedef struct hsc_vhistory {         /* every attempted txn, host pointers */
+    size_t nops; uint32_t ntxn;
+    const uint32_t *txn;              /* [nops] < ntxn */
+    const uint64_t *key;              /* [nops] */
+    const uint8_t  *is_write;         /* [nops] */
+    const uint64_t *value;            /* [nops] write: the value written; read: the value returned */
+    const uint8_t  *status;           /* [ntxn] HSC_TXN_* */
+} hsc_vhistory;
+#define HSC_RESOLVE_ARRAYS 1   /* flags: also copy the per-op arrays back */
+#define HSC_RESOLVE_LIST_CAP 4096
+typedef struct hsc_resolved {
+    size_t nops, kept_ops;  uint32_t ntxn, ncommitted, recovered, aborted, dropped;
+    uint64_t writes, reads;
+    uint64_t g1a_reads, g1b_reads, dangling_reads, internal_reads;  /* reads of txns in C */
+    uint32_t g1a_txns, g1b_txns;
+    const uint8_t *fate;         /* [ntxn] 0 committed, 1 aborted, 2 dropped, 3 recovered */
+    const uint32_t *cid;         /* [ntxn] */
+    const uint32_t *txn_of_cid;  /* [ncommitted] */
+    const uint8_t *txn_g1;       /* [ntxn] */
+    uint32_t n_listed;           /* min(cap, reads of C flagged ABORTED | INTERMEDIATE | DANGLING) */
+    const uint64_t *listed_op, *listed_wop;  /* ascending read op index; its write op (UINT64_MAX: none) */
+    const uint32_t *obs_txn;     /* [nops] input ids; 0xFFFFFFFF initial or a write op; 0xFFFFFFFE none.  NULL without ARRAYS */
+    const uint64_t *obs_op;      /* [nops] the write op observed, UINT64_MAX none */
+    const uint8_t  *rflag;       /* [nops] HSC_RD_* */
+    uint32_t sweeps;  float ms;  /* recovery sweeps run; device time of the whole call */
+} hsc_resolved;
+int hsc_dep_graph_resolve(hsc_ctx *ctx, const hsc_vhistory *h, unsigned flags, hsc_resolved *out);
+/* hsc_dep_graph_build_device over the lowered ops of the last resolve (ncommitted txns); joins staged
+ * rw pairs / real-time edges like any build.  HSC_ESTATE without a resolve. */
+int hsc_dep_graph_build_resolved(hsc_ctx *ctx, int flags, hsc_graph_stats *stats);
+/* How the last resolve sorted its writers: bit 0 the (key, value) lookup table,
+ * bit 1 the (key, txn) finality rows -- set: as packed single words, clear: by
+ * whole rows (or nothing to sort). */
+int hsc_dep_graph_resolve_sort_path(hsc_ctx *ctx);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst

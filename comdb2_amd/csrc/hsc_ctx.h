@@ -1,6 +1,7 @@
 // hsc_ctx.h -- the validator context (struct hsc_ctx) and the host-side
-// types it holds, shared by hsc_host.cpp (single-GPU context) and
-// hsc_multi.cpp (the multi-GPU context built from member contexts).
+// types it holds, shared by hsc_host.cpp (single-GPU context),
+// hsc_graph_host.cpp (its dependency-graph entries) and hsc_multi.cpp (the
+// multi-GPU context built from member contexts).
 #pragma once
 #include "../../include/hip_serial.h"
 #include "hsc_internal.h"
@@ -303,6 +304,36 @@ struct alignas(128) MarshalPart {  // one per worker: no shared cache lines
         lock_table.clear(), lock_txn.clear();
         ix_last = ~0ull;  // the dictionary may have changed since the last marshal
         ix_groups = nullptr;
+    }
+};
+
+// A stretch of a stream's work timed with two events that live as long as
+// the span: every way out of the caller destroys them.  (Hidden: its
+// inline members stay out of the library's exported symbols.)
+struct __attribute__((visibility("hidden"))) EventSpan {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventSpan() = default;
+    EventSpan(const EventSpan &) = delete;
+    EventSpan &operator=(const EventSpan &) = delete;
+    ~EventSpan()
+    {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    hipError_t begin(hipStream_t s)
+    {
+        hipError_t e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e == hipSuccess) e = hipEventRecord(e0, s);
+        return e;
+    }
+    hipError_t end(hipStream_t s) { return hipEventRecord(e1, s); }
+    // after the stream is synchronised; 0 if an event is missing or the query fails
+    float ms() const
+    {
+        float t = 0;
+        if (!e0 || !e1 || hipEventElapsedTime(&t, e0, e1) != hipSuccess) return 0;
+        return t;
     }
 };
 
@@ -764,6 +795,18 @@ namespace hsc {
 // hsc_host.cpp internals the multi-GPU context (hsc_multi.cpp) drives its
 // member contexts with
 int ctx_fail(hsc_ctx *c, int code, const char *what, hipError_t e = hipSuccess);
+// A failed HIP call ends the function with HSC_EDEVICE and the call's text as
+// the context's error; a failed hsc call (rc != HSC_OK) with its rc.
+#define HIPCHK(c, call)                                                      \
+    do {                                                                     \
+        hipError_t e_ = (call);                                              \
+        if (e_ != hipSuccess) return hsc::ctx_fail((c), HSC_EDEVICE, #call, e_); \
+    } while (0)
+#define HIPCHK_RC(c, call)             \
+    do {                               \
+        const int rc_ = (call);        \
+        if (rc_ != HSC_OK) return rc_; \
+    } while (0)
 int ctx_window_words(hsc_ctx *c);
 void ctx_clear_window(hsc_ctx *c);
 int ctx_ensure_built(hsc_ctx *c);
@@ -778,7 +821,8 @@ int ctx_default_threads();
 void ctx_par_for(hsc_ctx *c, int nwork, const std::function<void(int)> &f);
 bool ctx_small_fits(hsc_ctx *c, size_t n_txn, size_t n, size_t n_lock);
 int ctx_edge_keys(hsc_ctx *c, uint32_t *gid, uint64_t *words);
-// op_txn: the last build's ops' txn array when still live (the op-range cut)
+// (hsc_graph_host.cpp) op_txn: the last build's ops' txn array when still
+// live (the op-range cut)
 int ctx_graph_cut(hsc_ctx *c, const uint8_t *cover, size_t *m, const uint64_t **rows,
                   const uint32_t *op_txn = nullptr, const uint64_t *op_key = nullptr,
                   const uint8_t *op_isw = nullptr);

@@ -187,12 +187,6 @@ static int fail(hsc_ctx *c, int code, const char *what, hipError_t e)
     return code;
 }
 
-#define HIPCHK(c, call)                                          \
-    do {                                                         \
-        hipError_t e_ = (call);                                  \
-        if (e_ != hipSuccess) return fail((c), HSC_EDEVICE, #call, e_); \
-    } while (0)
-
 // the bits of x under mask m, packed to the low end (MSB order kept)
 static uint64_t host_compress(uint64_t x, uint64_t m)
 {
@@ -331,14 +325,6 @@ static int window_words(hsc_ctx *c)
     for (auto &g : c->groups) W = std::max(W, (g.klen + 7) / 8);
     return W;
 }
-
-// Sort + dedupe rows staged in d_gid/d_words/d_lsn (n_in rows, stride cap),
-// then build group spans, tile maxima and table maxima.
-#define HIPCHK_RC(c, call)                  \
-    do {                                    \
-        const int rc_ = (call);             \
-        if (rc_ != HSC_OK) return rc_;      \
-    } while (0)
 
 // The window's distinct commit LSNs, sorted (commit ranks of the narrow
 // tiles), from the staged rows' LSNs before the key sort moves them: a log
@@ -695,6 +681,8 @@ static int code_sort(hsc_ctx *c, size_t n_in, bool *done)
     return HSC_OK;
 }
 
+// Sort + dedupe rows staged in d_gid/d_words/d_lsn (n_in rows, stride cap),
+// then build group spans, tile maxima and table maxima.
 static int device_build(hsc_ctx *c, size_t n_in)
 {
     BuildTrace bt(c->stream);
@@ -721,10 +709,8 @@ static int device_build(hsc_ctx *c, size_t n_in)
     HIPCHK(c, c->d_count.ensure(256));
     bt.stamp("alloc");
 
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventRecord(e0, s));
+    EventSpan build_t;
+    HIPCHK(c, build_t.begin(s));
     // varying key bits and the LSN span in one pass; the distinct commit list
     // only when snapshot ranks need its directory (a window spanning >= 2^32
     // of log): otherwise rows carry lsn - oldest + 1
@@ -1039,18 +1025,14 @@ static int device_build(hsc_ctx *c, size_t n_in)
             tiles32 = true;
         }
     }
-    HIPCHK(c, hipEventRecord(e1, s));
+    HIPCHK(c, build_t.end(s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (tiles32) c->ntiles32 = wide32 == 0;
     c->trad_shift = (int)trad_shift;
     bt.stamp("tiles");
     if (c->narrow && c->trad_m >= 64) HIPCHK_RC(c, narrow_trad_pick(c));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    c->last.ingest_ms = ms;
+    c->last.ingest_ms = build_t.ms();
     c->last.tiles = c->ntiles;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     // table maxima back to the host (device ingest computes them on the GPU)
     if (nt > 0) {
         HIPCHK(c, hipMemcpy(tm.data(), c->d_table_max.p, 8 * (size_t)nt, hipMemcpyDeviceToHost));
@@ -4602,591 +4584,6 @@ int hsc_enable_timing(hsc_ctx *c, int on)
 
 }  // extern "C"
 
-// Build c->graph from device-resident ops (edges and CSR/CSC), timed with
-// events.  Caller holds c->mu.
-static int graph_build_timed(hsc_ctx *c, const GraphInput &in, bool full, float *build_ms)
-{
-    hipStream_t s = c->stream;
-    GraphBufs &gb = c->graph;
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventRecord(e0, s));
-    GraphInput gi = in;
-    // staged rows that would index past the CSR arrays, or the real-time order
-    // of another history: the build fails and every staged edge is dropped
-    const bool bad_rw = gb.n_extra && c->x_max_txn >= in.ntxn;
-    const bool bad_rt = gb.rt_staged && gb.rt_ntxn != in.ntxn;
-    if (bad_rw || bad_rt) {
-        gb.n_extra = 0;
-        gb.rt_staged = false;
-        gb.n_rt = 0;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        return fail(c, HSC_EINVAL, bad_rw ? "a staged rw pair names a txn >= the build's ntxn"
-                                          : "the staged real-time order is of another ntxn than the build's");
-    }
-    if (gb.n_extra) {  // staged edges join this build, once
-        gi.x_rows = gb.x_rows.as<uint64_t>();
-        gi.x_type = gb.x_type.as<uint64_t>();
-        gi.n_extra = gb.n_extra;
-        gb.n_extra = 0;
-    }
-    if (gb.rt_staged) {  // and the staged real-time order, a segment of its own
-        gi.r_rows = gb.rt_rows.as<uint64_t>();
-        gi.r_type = gb.rt_type.as<uint64_t>();
-        gi.n_rt = gb.n_rt;
-        gb.rt_staged = false;
-        gb.n_rt = 0;
-    }
-    gb.edge_bad = nullptr;
-    gb.post = nullptr;
-    hipError_t e = graph_build(gi, gb, full, s);
-    if (e == hipSuccess) e = hipEventRecord(e1, s);
-    // with the sync: the backward rows listed and the edge pass's check of the
-    // observed ids (in.check)
-    uint32_t post[3] = {0, 0, 0};
-    if (e == hipSuccess && gb.post) e = hipMemcpyAsync(post, gb.post - 1, 12, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) (void)hipEventElapsedTime(build_ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    HIPCHK(c, e);
-    if (post[0] && gb.writer_packed) return fail(c, HSC_EDEVICE, "graph build: the writer sort's look-back stalled");
-    gb.back_n = post[1];
-    const uint32_t ebad = gb.edge_bad ? post[2] : 0;
-    gb.bad |= ebad;
-    if (ebad & 1) {
-        c->graph_ntxn = 0;
-        return fail(c, HSC_EINVAL, "history op out of range");
-    }
-    c->graph_ntxn = in.ntxn;
-    return HSC_OK;
-}
-
-// Upload a history and build its graph into c->graph (edges and CSR/CSC).
-// Caller holds c->mu.
-static int graph_upload_build(hsc_ctx *c, const hsc_history *h, bool full, float *build_ms,
-                              bool skip_rw = false)
-{
-    if (!h || (h->nops && (!h->txn || !h->key || !h->is_write || !h->observed)) ||
-        h->nops > 0x7FFFFFFFull)
-        return HSC_EINVAL;
-    if (c->host_only) return fail(c, HSC_EDEVICE, "host-only context");
-    (void)hipSetDevice(c->device);
-    for (size_t i = 0; i < h->nops; ++i)
-        if (h->txn[i] >= h->ntxn || h->observed[i] >= (int64_t)h->ntxn || h->observed[i] < -1)
-            return fail(c, HSC_EINVAL, "history op out of range");
-    hipStream_t s = c->stream;
-    GraphBufs &gb = c->graph;
-    const size_t n = h->nops;
-    std::vector<uint32_t> obs(std::max<size_t>(n, 1));
-    for (size_t i = 0; i < n; ++i) obs[i] = h->observed[i] < 0 ? 0xFFFFFFFFu : (uint32_t)h->observed[i];
-    HIPCHK(c, gb.h_txn.ensure(4 * std::max<size_t>(n, 1)));
-    HIPCHK(c, gb.h_key.ensure(8 * std::max<size_t>(n, 1)));
-    HIPCHK(c, gb.h_isw.ensure(std::max<size_t>(n, 1)));
-    HIPCHK(c, gb.h_obs.ensure(4 * std::max<size_t>(n, 1)));
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(gb.h_txn.p, h->txn, 4 * n, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(gb.h_key.p, h->key, 8 * n, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(gb.h_isw.p, h->is_write, n, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(gb.h_obs.p, obs.data(), 4 * n, hipMemcpyHostToDevice, s));
-    }
-    GraphInput in{gb.h_txn.as<uint32_t>(), gb.h_key.as<uint64_t>(), gb.h_isw.as<uint8_t>(),
-                  gb.h_obs.as<uint32_t>(), n, h->ntxn};
-    in.skip_rw = skip_rw;
-    return graph_build_timed(c, in, full, build_ms);
-}
-
-// Edge and edge-type counts of c->graph into st (none after a raw build).
-static int graph_edge_stats(hsc_ctx *c, hsc_graph_stats *st)
-{
-    GraphBufs &gb = c->graph;
-    st->edges = gb.ne;
-    uint64_t t[3] = {0, 0, 0};
-    HIPCHK(c, graph_type_counts(gb, t, c->stream));
-    st->ww = t[0];
-    st->wr = t[1];
-    st->rw = t[2];
-    return HSC_OK;
-}
-
-static void scc_size_stats(const uint32_t *scc, uint32_t ntxn, hsc_graph_stats *st)
-{
-    std::vector<uint32_t> sz(std::max<uint32_t>(ntxn, 1), 0);
-    for (uint32_t v = 0; v < ntxn; ++v)
-        if (scc[v] < ntxn) sz[scc[v]]++;
-    for (uint32_t v = 0; v < ntxn; ++v)
-        if (sz[v] > 1) {
-            st->nontrivial_sccs++;
-            st->txns_in_cycles += sz[v];
-        }
-}
-
-extern "C" {
-
-int hsc_dep_graph_scc(hsc_ctx *c, const hsc_history *h, uint32_t *scc_out, hsc_graph_stats *st)
-{
-    if (!c || !h || (h->ntxn && !scc_out)) return HSC_EINVAL;
-    MuGuard g(c);
-    float build_ms = 0;
-    int rc = graph_upload_build(c, h, true, &build_ms);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    GraphBufs &gb = c->graph;
-    hipEvent_t e1, e2;
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventCreate(&e2));
-    HIPCHK(c, hipEventRecord(e1, s));
-    uint32_t rounds = 0, iters = 0;
-    HIPCHK(c, graph_scc(h->ntxn, gb, &rounds, &iters, s));
-    HIPCHK(c, hipEventRecord(e2, s));
-    if (h->ntxn)
-        HIPCHK(c, hipMemcpyAsync(scc_out, gb.scc.p, 4 * (size_t)h->ntxn, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (st) {
-        memset(st, 0, sizeof *st);
-        st->build_ms = build_ms;
-        (void)hipEventElapsedTime(&st->scc_ms, e1, e2);
-        rc = graph_edge_stats(c, st);
-        if (rc) return rc;
-        scc_size_stats(scc_out, h->ntxn, st);
-        st->rounds = rounds;
-        st->iterations = iters;
-    }
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(e2);
-    return HSC_OK;
-}
-
-int hsc_dep_graph_build(hsc_ctx *c, const hsc_history *h, int flags, hsc_graph_stats *st)
-{
-    if (!c || !h) return HSC_EINVAL;
-    MuGuard g(c);
-    float build_ms = 0;
-    int rc = graph_upload_build(c, h, (flags & HSC_GRAPH_FULL) != 0, &build_ms,
-                                (flags & HSC_GRAPH_NO_RW) != 0);
-    if (rc || !st) return rc;
-    memset(st, 0, sizeof *st);
-    st->build_ms = build_ms;
-    return graph_edge_stats(c, st);
-}
-
-int hsc_dep_graph_build_device(hsc_ctx *c, size_t nops, uint32_t ntxn, const uint32_t *txn_dev,
-                               const uint64_t *key_dev, const uint8_t *is_write_dev,
-                               const uint32_t *observed_dev, int flags, hsc_graph_stats *st)
-{
-    if (!c || (nops && (!txn_dev || !key_dev || !is_write_dev || !observed_dev)) ||
-        nops > 0x7FFFFFFFull)
-        return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    GraphInput in{txn_dev, key_dev, is_write_dev, observed_dev, nops, ntxn};
-    in.skip_rw = (flags & HSC_GRAPH_NO_RW) != 0;
-    in.check = true;  // the ids and the txn order, in the build's first pass
-    float build_ms = 0;
-    int rc = graph_build_timed(c, in, (flags & HSC_GRAPH_FULL) != 0, &build_ms);
-    if (rc && (c->graph.bad & 1)) return fail(c, HSC_EINVAL, "history op out of range");
-    if (rc || !st) return rc;
-    memset(st, 0, sizeof *st);
-    st->build_ms = build_ms;
-    return graph_edge_stats(c, st);
-}
-
-int hsc_dep_graph_resolve(hsc_ctx *c, const hsc_vhistory *h, unsigned flags, hsc_resolved *out)
-{
-    if (!c || !h || !out || (h->nops && (!h->txn || !h->key || !h->is_write || !h->value)) ||
-        (h->ntxn && !h->status) || h->nops > 0x7FFFFFFFull || h->ntxn > 0x7FFFFFFFu)
-        return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    hipStream_t s = c->stream;
-    static const int dir_bits = [] {  // (A/B diagnostics: 0 = the plain binary search)
-        const char *v = getenv("HSC_RESOLVE_DIR_BITS");
-        return v ? atoi(v) : -1;
-    }();
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
-    ResolveOut &o = c->resolve_out;
-    const ResolveIn in{h->nops, h->ntxn, h->txn, h->key, h->is_write, h->value, h->status};
-    hipError_t e = hipEventRecord(e0, s);
-    if (e == hipSuccess) e = graph_resolve(in, c->resolve, (flags & HSC_RESOLVE_ARRAYS) != 0, dir_bits, o, s);
-    const int bad = o.bad;
-    if (e == hipSuccess) e = hipEventRecord(e1, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    memset(out, 0, sizeof *out);
-    if (e == hipSuccess) (void)hipEventElapsedTime(&out->ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (e == hipErrorInvalidValue && bad)
-        return fail(c, HSC_EINVAL,
-                    bad & 1   ? "value history: an op names a txn >= ntxn"
-                    : bad & 2 ? "value history: a write of HSC_VAL_INIT"
-                    : bad & 4 ? "value history: a status above HSC_TXN_UNKNOWN"
-                              : "value history: a written (key, value) occurs twice");
-    HIPCHK(c, e);
-    // (never a null array: an empty vector's data() may be)
-    static const uint8_t none8[1] = {0};
-    static const uint32_t none32[1] = {0};
-    static const uint64_t none64[1] = {0};
-    out->nops = h->nops;
-    out->kept_ops = o.kept_ops;
-    out->ntxn = h->ntxn;
-    out->ncommitted = o.ncommitted;
-    out->recovered = o.recovered;
-    out->aborted = o.aborted;
-    out->dropped = o.dropped;
-    out->writes = o.writes;
-    out->reads = o.reads;
-    out->g1a_reads = o.g1a_reads;
-    out->g1b_reads = o.g1b_reads;
-    out->dangling_reads = o.dangling_reads;
-    out->internal_reads = o.internal_reads;
-    out->g1a_txns = o.g1a_txns;
-    out->g1b_txns = o.g1b_txns;
-    out->fate = o.fate.empty() ? none8 : o.fate.data();
-    out->cid = o.cid.empty() ? none32 : o.cid.data();
-    out->txn_of_cid = o.txn_of_cid.empty() ? none32 : o.txn_of_cid.data();
-    out->txn_g1 = o.txn_g1.empty() ? none8 : o.txn_g1.data();
-    out->n_listed = o.n_listed;
-    out->listed_op = o.listed_op.empty() ? none64 : o.listed_op.data();
-    out->listed_wop = o.listed_wop.empty() ? none64 : o.listed_wop.data();
-    if (flags & HSC_RESOLVE_ARRAYS) {
-        out->obs_txn = o.obs_txn.empty() ? none32 : o.obs_txn.data();
-        out->obs_op = o.obs_op.empty() ? none64 : o.obs_op.data();
-        out->rflag = o.rflag.empty() ? none8 : o.rflag.data();
-    }
-    out->sweeps = o.sweeps;
-    return HSC_OK;
-}
-
-int hsc_dep_graph_build_resolved(hsc_ctx *c, int flags, hsc_graph_stats *st)
-{
-    if (!c) return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    const ResolveBufs &r = c->resolve;
-    if (!r.valid) return fail(c, HSC_ESTATE, "no resolved history (hsc_dep_graph_resolve)");
-    GraphInput in{r.l_txn.as<uint32_t>(), r.l_key.as<uint64_t>(), r.l_isw.as<uint8_t>(), r.l_obs.as<uint32_t>(),
-                  r.kept, r.nc};
-    in.skip_rw = (flags & HSC_GRAPH_NO_RW) != 0;
-    in.check = true;  // finds whether the kept ops are in txn order
-    float build_ms = 0;
-    int rc = graph_build_timed(c, in, (flags & HSC_GRAPH_FULL) != 0, &build_ms);
-    if (rc || !st) return rc;
-    memset(st, 0, sizeof *st);
-    st->build_ms = build_ms;
-    return graph_edge_stats(c, st);
-}
-
-int hsc_dep_graph_resolve_sort_path(hsc_ctx *c) { return c ? c->resolve.sort_path : 0; }
-
-int hsc_dep_graph_stage_rw_pairs(hsc_ctx *c, uint32_t nrs, const uint32_t *readset_txn,
-                                 size_t ncommit, const uint64_t *commit_lsn,
-                                 const uint32_t *commit_txn)
-{
-    if (!c || (nrs && !readset_txn) || (ncommit && (!commit_lsn || !commit_txn)))
-        return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    for (size_t i = 1; i < ncommit; ++i)
-        if (commit_lsn[i] <= commit_lsn[i - 1]) return fail(c, HSC_EINVAL, "commit LSNs not sorted");
-    hipStream_t s = c->stream;
-    GraphBufs &gb = c->graph;
-    const size_t n = c->e_dev_n;
-    gb.n_extra = 0;
-    // every endpoint a pair can map to; graph_build_timed rejects the staged
-    // rows if the build's ntxn does not cover them
-    uint32_t xm = 0;
-    for (uint32_t i = 0; i < nrs; ++i) xm = std::max(xm, readset_txn[i]);
-    for (size_t i = 0; i < ncommit; ++i) xm = std::max(xm, commit_txn[i]);
-    c->x_max_txn = xm;
-    if (n == 0) return HSC_OK;
-    // mapping tables next to each other: rs_txn[nrs] | commit_txn[ncommit] | commit_lsn[ncommit]
-    const size_t o_ct = ((size_t)nrs + 1) & ~(size_t)1, o_cl = o_ct + ncommit + (ncommit & 1);
-    HIPCHK(c, gb.x_map.ensure(4 * (o_cl + 2 * ncommit) + 64));
-    uint32_t *m32 = gb.x_map.as<uint32_t>();
-    uint64_t *cl = (uint64_t *)(m32 + o_cl);
-    uint32_t *bad = m32 + o_cl + 2 * ncommit;
-    if (nrs) HIPCHK(c, hipMemcpyAsync(m32, readset_txn, 4 * (size_t)nrs, hipMemcpyHostToDevice, s));
-    if (ncommit) {
-        HIPCHK(c, hipMemcpyAsync(m32 + o_ct, commit_txn, 4 * ncommit, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(cl, commit_lsn, 8 * ncommit, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(c, hipMemsetAsync(bad, 0, 4, s));
-    HIPCHK(c, gb.x_rows.ensure(8 * n));
-    HIPCHK(c, gb.x_type.ensure(8 * n));
-    HIPCHK(c, graph_pairs_rows(n, c->e_dev_txn, c->e_dev_lsn, nrs, m32, ncommit, cl, m32 + o_ct,
-                               gb.x_rows.as<uint64_t>(), gb.x_type.as<uint64_t>(), bad, s));
-    uint32_t hb = 0;
-    HIPCHK(c, hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (hb) return fail(c, HSC_EINVAL, "rw pair names a writer LSN or read set not in the map");
-    gb.n_extra = n;
-    return HSC_OK;
-}
-
-int hsc_dep_graph_stage_realtime(hsc_ctx *c, uint32_t ntxn, const uint64_t *invoke, const uint64_t *complete,
-                                 uint64_t *n_edges, float *ms)
-{
-    if (!c || (ntxn && (!invoke || !complete))) return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    GraphBufs &gb = c->graph;
-    gb.rt_staged = false;  // a second call replaces the first; a failed one stages nothing
-    gb.n_rt = 0;
-    if (n_edges) *n_edges = 0;
-    if (ms) *ms = 0;
-    for (uint32_t v = 0; v < ntxn; ++v)
-        if (invoke[v] > complete[v]) return fail(c, HSC_EINVAL, "a txn completes before its invoke");
-    hipStream_t s = c->stream;
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
-    hipError_t e = hipEventRecord(e0, s);
-    if (e == hipSuccess) e = realtime_stage(ntxn, invoke, complete, gb, s);
-    const bool too_many = e == hipErrorInvalidValue;
-    if (e == hipSuccess) e = hipEventRecord(e1, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && ms) (void)hipEventElapsedTime(ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (too_many) return fail(c, HSC_EINVAL, "the real-time order has more edges than a build takes");
-    if (e != hipSuccess) gb.n_rt = 0;
-    HIPCHK(c, e);
-    gb.rt_staged = true;
-    if (n_edges) *n_edges = gb.n_rt;
-    return HSC_OK;
-}
-
-int hsc_dep_graph_scc_built(hsc_ctx *c, uint32_t *scc_out, hsc_graph_stats *st)
-{
-    if (!c) return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    GraphBufs &gb = c->graph;
-    const uint32_t nn = c->graph_ntxn;
-    if (nn && !scc_out) return HSC_EINVAL;
-    if (gb.raw) return fail(c, HSC_ESTATE, "last build kept raw rows only (no HSC_GRAPH_FULL)");
-    hipStream_t s = c->stream;
-    hipEvent_t e1, e2;
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventCreate(&e2));
-    HIPCHK(c, hipEventRecord(e1, s));
-    uint32_t rounds = 0, iters = 0;
-    HIPCHK(c, graph_scc(nn, gb, &rounds, &iters, s));
-    HIPCHK(c, hipEventRecord(e2, s));
-    if (nn) HIPCHK(c, hipMemcpyAsync(scc_out, gb.scc.p, 4 * (size_t)nn, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (st) {
-        memset(st, 0, sizeof *st);
-        (void)hipEventElapsedTime(&st->scc_ms, e1, e2);
-        const int rc = graph_edge_stats(c, st);
-        if (rc) return rc;
-        scc_size_stats(scc_out, nn, st);
-        st->rounds = rounds;
-        st->iterations = iters;
-    }
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(e2);
-    return HSC_OK;
-}
-
-int hsc_dep_graph_anomalies(hsc_ctx *c, unsigned flags, unsigned max_anti_batches, hsc_anomalies *out)
-{
-    if (!c || !out) return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    GraphBufs &gb = c->graph;
-    const uint32_t nn = c->graph_ntxn;
-    if (gb.raw) return fail(c, HSC_ESTATE, "last build kept raw rows only (no HSC_GRAPH_FULL)");
-    hipStream_t s = c->stream;
-    hipEvent_t e1, e2;
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventCreate(&e2));
-    HIPCHK(c, hipEventRecord(e1, s));
-    AnomOut &o = c->anom_out;
-    hipError_t e = graph_anomalies(nn, gb, c->anom, (flags & HSC_ANOM_WITNESS) != 0, max_anti_batches, o, s);
-    if (e == hipSuccess) e = hipEventRecord(e2, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    memset(out, 0, sizeof *out);
-    if (e == hipSuccess) (void)hipEventElapsedTime(&out->ms, e1, e2);
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(e2);
-    HIPCHK(c, e);
-    // (never a null array: an empty vector's data() may be)
-    static const uint8_t none8[1] = {0};
-    static const uint32_t none32[1] = {0};
-    out->ntxn = nn;
-    out->cls = o.cls.empty() ? none8 : o.cls.data();
-    out->ncomp = (uint32_t)o.comp_label.size();
-    out->comp_label = o.comp_label.empty() ? none32 : o.comp_label.data();
-    out->comp_class = o.comp_class.empty() ? none8 : o.comp_class.data();
-    if (o.wit_off.size() != (size_t)out->ncomp + 1) o.wit_off.assign((size_t)out->ncomp + 1, 0);
-    out->wit_off = o.wit_off.data();
-    out->wit_txn = o.wit_txn.empty() ? none32 : o.wit_txn.data();
-    out->wit_type = o.wit_type.empty() ? none8 : o.wit_type.data();
-    for (int k = 0; k < 3; ++k) {
-        out->comps[k] = o.comps[k];
-        out->txns[k] = o.txns[k];
-    }
-    out->anti_edges = o.anti_edges;
-    out->anti_tested = o.anti_tested;
-    out->core_nodes = o.core_nodes;
-    out->reach_batches = o.reach_batches;
-    out->sweeps = (uint32_t)std::min<uint64_t>(o.sweeps, 0xFFFFFFFFull);
-    out->bfs_levels = o.bfs_levels;
-    return HSC_OK;
-}
-
-int hsc_dep_graph_si(hsc_ctx *c, unsigned flags, hsc_si_report *out)
-{
-    if (!c || !out) return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    GraphBufs &gb = c->graph;
-    const uint32_t nn = c->graph_ntxn;
-    if (gb.raw) return fail(c, HSC_ESTATE, "last build kept raw rows only (no HSC_GRAPH_FULL)");
-    hipStream_t s = c->stream;
-    hipEvent_t e1, e2;
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventCreate(&e2));
-    HIPCHK(c, hipEventRecord(e1, s));
-    SiOut &o = c->si_out;
-    hipError_t e = graph_si(nn, gb, c->si, (flags & HSC_SI_WITNESS) != 0, o, s);
-    const bool too_big = o.too_big;
-    if (e == hipSuccess) e = hipEventRecord(e2, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    memset(out, 0, sizeof *out);
-    if (e == hipSuccess) (void)hipEventElapsedTime(&out->ms, e1, e2);
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(e2);
-    // (never a null array: an empty vector's data() may be)
-    static const uint8_t none8[1] = {0};
-    static const uint32_t none32[2] = {0, 0};
-    if (e != hipSuccess) {
-        o.clear(0);
-        out->nonadj = out->comp_nonadj = out->wit_type = none8;
-        out->comp_label = out->wit_off = out->wit_txn = none32;
-        if (too_big) return fail(c, HSC_EINVAL, "the product graph does not fit 32-bit node or edge ids");
-    }
-    HIPCHK(c, e);
-    out->ntxn = nn;
-    out->nonadj = o.nonadj.empty() ? none8 : o.nonadj.data();
-    out->ncomp = (uint32_t)o.comp_label.size();
-    out->comp_label = o.comp_label.empty() ? none32 : o.comp_label.data();
-    out->comp_nonadj = o.comp_nonadj.empty() ? none8 : o.comp_nonadj.data();
-    if (o.wit_off.size() != (size_t)out->ncomp + 1) o.wit_off.assign((size_t)out->ncomp + 1, 0);
-    out->wit_off = o.wit_off.data();
-    out->wit_txn = o.wit_txn.empty() ? none32 : o.wit_txn.data();
-    out->wit_type = o.wit_type.empty() ? none8 : o.wit_type.data();
-    out->comps = o.comps;
-    out->txns = o.txns;
-    out->core_nodes = o.core_nodes;
-    out->product_nodes = o.product_nodes;
-    out->product_edges = o.product_edges;
-    out->scc_rounds = o.scc_rounds;
-    out->scc_iterations = o.scc_iterations;
-    out->bfs_levels = o.bfs_levels;
-    return HSC_OK;
-}
-
-int hsc_dep_graph_cover(hsc_ctx *c, uint8_t *cover_dev)
-{
-    if (!c || (c->graph_ntxn && !cover_dev)) return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    HIPCHK(c, graph_cover(c->graph, c->graph_ntxn, cover_dev, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HSC_OK;
-}
-
-int hsc_dep_graph_cut(hsc_ctx *c, const uint8_t *cover_dev, uint64_t *rows_dev, size_t cap,
-                      size_t *m)
-{
-    if (!c || !m || (c->graph_ntxn && !cover_dev)) return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    HIPCHK(c, graph_cut(c->graph, cover_dev, m, c->stream));
-    const size_t k = std::min(cap, *m);
-    if (k && rows_dev)
-        HIPCHK(c, hipMemcpyAsync(rows_dev, c->graph.cut.p, 8 * k, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HSC_OK;
-}
-
-int hsc_dep_graph_scc_cut(hsc_ctx *c, uint32_t ntxn, const uint8_t *cover_dev,
-                          const uint64_t *rows_dev, size_t m, uint32_t *scc_dev,
-                          hsc_graph_stats *st)
-{
-    if (!c || (ntxn && (!cover_dev || !scc_dev)) || (m && !rows_dev) || m > 0xFFFFFFFFull)
-        return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    hipStream_t s = c->stream;
-    hipEvent_t e1, e2;
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventCreate(&e2));
-    HIPCHK(c, hipEventRecord(e1, s));
-    uint32_t rounds = 0, iters = 0, nc = 0;
-    hipError_t e = graph_scc_rows(ntxn, cover_dev, rows_dev, m, c->subgraph, scc_dev, &nc, &rounds,
-                                  &iters, s);
-    if (e == hipErrorInvalidValue) {
-        (void)hipEventDestroy(e1);
-        (void)hipEventDestroy(e2);
-        return fail(c, HSC_EINVAL, "cut row outside the cover");
-    }
-    HIPCHK(c, e);
-    HIPCHK(c, hipEventRecord(e2, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (st) {
-        memset(st, 0, sizeof *st);
-        st->edges = c->subgraph.ne;
-        (void)hipEventElapsedTime(&st->scc_ms, e1, e2);
-        st->rounds = rounds;
-        st->iterations = iters;
-        st->cut_nodes = nc;
-        // components of >= 2 txns live in the cut: its nc colours suffice
-        std::vector<uint32_t> h(std::max<uint32_t>(nc, 1));
-        if (nc) HIPCHK(c, hipMemcpy(h.data(), c->subgraph.scc.p, 4 * (size_t)nc, hipMemcpyDeviceToHost));
-        scc_size_stats(h.data(), nc, st);
-    }
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(e2);
-    return HSC_OK;
-}
-
-int hsc_dep_graph_edges(hsc_ctx *c, uint32_t *src, uint32_t *dst, uint32_t *type, size_t cap,
-                        size_t *n)
-{
-    if (!c || !n) return HSC_EINVAL;
-    if (c->host_only) return HSC_EDEVICE;
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    GraphBufs &gb = c->graph;
-    *n = gb.ne;
-    const size_t m = std::min(cap, gb.ne);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (m && src) HIPCHK(c, hipMemcpy(src, gb.src.p, 4 * m, hipMemcpyDeviceToHost));
-    if (m && dst) HIPCHK(c, hipMemcpy(dst, gb.out_dst.p, 4 * m, hipMemcpyDeviceToHost));
-    if (m && type) HIPCHK(c, hipMemcpy(type, gb.type.p, 4 * m, hipMemcpyDeviceToHost));
-    return HSC_OK;
-}
-
-}  // extern "C"
-
 // ---- internals the multi-GPU context drives its members with (hsc_ctx.h) ----
 namespace hsc {
 int ctx_fail(hsc_ctx *c, int code, const char *what, hipError_t e) { return fail(c, code, what, e); }
@@ -5219,19 +4616,6 @@ int ctx_edge_keys(hsc_ctx *c, uint32_t *gid, uint64_t *words)
         HIPCHK(c, hipMemcpy(words + c->W + j, c->d_words.as<uint64_t>() + (size_t)j * c->cap + last, 8,
                             hipMemcpyDeviceToHost));
     }
-    return HSC_OK;
-}
-
-// The cut of the last build under cover (one pass: count + rows); *rows
-// points into the context's own buffer until its next graph call.
-int ctx_graph_cut(hsc_ctx *c, const uint8_t *cover, size_t *m, const uint64_t **rows, const uint32_t *op_txn,
-                  const uint64_t *op_key, const uint8_t *op_isw)
-{
-    MuGuard g(c);
-    (void)hipSetDevice(c->device);
-    HIPCHK(c, graph_cut(c->graph, cover, m, c->stream, op_txn, op_key, op_isw, false));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *rows = c->graph.cut.as<uint64_t>();
     return HSC_OK;
 }
 

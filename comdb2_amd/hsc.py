@@ -400,6 +400,14 @@ def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
+def _copy_out(p, n, dt) -> np.ndarray:
+    """A copy of the n elements of dtype dt at the library's pointer p."""
+    if n == 0:
+        return np.zeros(0, dt)
+    return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)),
+                                 shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+
+
 def _names(tbnames: Sequence[str]):
     arr = (C.c_char_p * max(1, len(tbnames)))()
     for i, n in enumerate(tbnames):
@@ -1026,9 +1034,7 @@ class Validator:
     # dependency graph + SCC (A10)
     def dep_graph_scc(self, h) -> tuple:
         """(scc[ntxn] = largest txn id of each txn's SCC, stats dict)."""
-        cols = [np.ascontiguousarray(h.txn, np.uint32), np.ascontiguousarray(h.key, np.uint64),
-                np.ascontiguousarray(h.is_write, np.uint8), np.ascontiguousarray(h.observed, np.int64)]
-        hs = _History(len(cols[0]), h.ntxn, *[c.ctypes.data for c in cols])
+        hs, keep = self._history(h)
         out = np.zeros(max(1, h.ntxn), dtype=np.uint32)
         st = GraphStats()
         self._chk(self.lib.hsc_dep_graph_scc(self.ctx, C.byref(hs), out.ctypes.data, C.byref(st)),
@@ -1140,11 +1146,7 @@ class Validator:
                                                    max_anti_batches, C.byref(a)),
                   "hsc_dep_graph_anomalies")
 
-        def arr(p, n, dt):
-            if n == 0:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)),
-                                         shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+        arr = _copy_out
 
         nc = a.ncomp
         off = arr(a.wit_off, nc + 1, np.uint32)
@@ -1172,11 +1174,7 @@ class Validator:
         self._chk(self.lib.hsc_dep_graph_si(self.ctx, SI_WITNESS if witness else 0, C.byref(a)),
                   "hsc_dep_graph_si")
 
-        def arr(p, n, dt):
-            if n == 0:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)),
-                                         shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+        arr = _copy_out
 
         nc = a.ncomp
         off = arr(a.wit_off, nc + 1, np.uint32)
@@ -1208,11 +1206,7 @@ class Validator:
         self._chk(self.lib.hsc_dep_graph_resolve(self.ctx, C.byref(hs), RESOLVE_ARRAYS if arrays else 0,
                                                  C.byref(a)), "hsc_dep_graph_resolve")
 
-        def arr(p, n, dt):
-            if n == 0:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)),
-                                         shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+        arr = _copy_out
 
         out = {k: getattr(a, k) for k in ("nops", "kept_ops", "ntxn", "ncommitted", "recovered", "aborted",
                                           "dropped", "writes", "reads", "g1a_reads", "g1b_reads",

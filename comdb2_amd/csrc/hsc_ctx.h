@@ -712,6 +712,8 @@ struct hsc_ctx {
     SiOut si_out;
     ResolveBufs resolve;     // hsc_dep_graph_resolve: device scratch and the lowered ops, host results
     ResolveOut resolve_out;
+    ListBufs lists;          // hsc_dep_graph_resolve_lists: device scratch and the edge rows, host results
+    ListOut lists_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

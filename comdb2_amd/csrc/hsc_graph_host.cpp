@@ -288,6 +288,89 @@ int hsc_dep_graph_build_resolved(hsc_ctx *c, int flags, hsc_graph_stats *st)
 
 int hsc_dep_graph_resolve_sort_path(hsc_ctx *c) { return c ? c->resolve.sort_path : 0; }
 
+int hsc_dep_graph_resolve_lists(hsc_ctx *c, const hsc_lhistory *h, unsigned flags, hsc_lresolved *out)
+{
+    if (!c || !h || !out || (h->nops && (!h->txn || !h->key || !h->is_write || !h->value || !h->list_off)) ||
+        (h->ntxn && !h->status) || h->nops > 0x7FFFFFFFull || h->ntxn > 0x7FFFFFFFu)
+        return HSC_EINVAL;
+    const uint64_t ne = h->nops ? h->list_off[h->nops] : 0;
+    if (ne > 0x7FFFFFFFull || (ne && !h->elems)) return HSC_EINVAL;
+    GRAPH_ENTRY(c);
+    hipStream_t s = c->stream;
+    EventSpan t;
+    ListOut &o = c->lists_out;
+    const ListIn in{h->nops, h->ntxn, h->txn, h->key, h->is_write, h->value, h->list_off, h->elems, h->status};
+    hipError_t e = t.begin(s);
+    if (e == hipSuccess) e = graph_resolve_lists(in, c->lists, (flags & HSC_RESOLVE_ARRAYS) != 0, o, s);
+    const int bad = o.bad;
+    if (e == hipSuccess) e = t.end(s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    memset(out, 0, sizeof *out);
+    if (e == hipErrorInvalidValue && bad)
+        return ctx_fail(c, HSC_EINVAL,
+                        bad & 1   ? "list history: an op names a txn >= ntxn"
+                        : bad & 2 ? "list history: list_off is not ascending"
+                        : bad & 4 ? "list history: a status above HSC_TXN_UNKNOWN"
+                                  : "list history: an appended (key, element) occurs twice");
+    HIPCHK(c, e);
+    out->ms = t.ms();
+    out->nops = h->nops;
+    out->ntxn = h->ntxn;
+    out->ncommitted = o.ncommitted;
+    out->recovered = o.recovered;
+    out->aborted = o.aborted;
+    out->dropped = o.dropped;
+    out->appends = o.appends;
+    out->reads = o.reads;
+    out->elements = o.elements;
+    out->keys = o.keys;
+    out->incompatible_keys = o.incompatible_keys;
+    out->spine_elements = o.spine_elements;
+    out->chain_entries = o.chain_entries;
+    out->ww = o.ww;
+    out->wr = o.wr;
+    out->rw = o.rw;
+    out->g1a_reads = o.g1a_reads;
+    out->g1b_reads = o.g1b_reads;
+    out->dangling_reads = o.dangling_reads;
+    out->duplicate_reads = o.duplicate_reads;
+    out->incompatible_reads = o.incompatible_reads;
+    out->internal_reads = o.internal_reads;
+    out->unobserved_appends = o.unobserved_appends;
+    out->g1a_txns = o.g1a_txns;
+    out->g1b_txns = o.g1b_txns;
+    out->fate = data_or_zero(o.fate);
+    out->cid = data_or_zero(o.cid);
+    out->txn_of_cid = data_or_zero(o.txn_of_cid);
+    out->txn_g1 = data_or_zero(o.txn_g1);
+    out->n_listed = o.n_listed;
+    out->listed_op = data_or_zero(o.listed_op);
+    out->listed_flag = data_or_zero(o.listed_flag);
+    out->rflag = data_or_zero(o.rflag);
+    out->spine_op = data_or_zero(o.spine_op);
+    return HSC_OK;
+}
+
+int hsc_dep_graph_build_lists(hsc_ctx *c, int flags, hsc_graph_stats *st)
+{
+    if (!c) return HSC_EINVAL;
+    GRAPH_ENTRY(c);
+    const ListBufs &l = c->lists;
+    if (!l.valid) return ctx_fail(c, HSC_ESTATE, "no resolved list history (hsc_dep_graph_resolve_lists)");
+    // the entry's rows take the staged pairs' slot: both cannot join one build
+    if (c->graph.n_extra)
+        return ctx_fail(c, HSC_EINVAL, "staged rw pairs cannot join a build from a list history");
+    // no ops: graph_build finds no writers, emits no edges of its own and
+    // sorts the rows of the x slot (holes dropped) like any staged rows
+    GraphInput in{nullptr, nullptr, nullptr, nullptr, 0, l.nc};
+    in.x_rows = l.x_rows.as<uint64_t>();
+    in.x_type = l.x_type.as<uint64_t>();
+    in.n_extra = l.n_rows;
+    float build_ms = 0;
+    const int rc = graph_build_timed(c, in, (flags & HSC_GRAPH_FULL) != 0, &build_ms);
+    return build_stats(c, rc, build_ms, st);
+}
+
 int hsc_dep_graph_stage_rw_pairs(hsc_ctx *c, uint32_t nrs, const uint32_t *readset_txn,
                                  size_t ncommit, const uint64_t *commit_lsn,
                                  const uint32_t *commit_txn)

@@ -760,6 +760,67 @@ struct ResolveOut {  // host results (hsc_resolved points into them)
 hipError_t graph_resolve(const ResolveIn &in, ResolveBufs &r, bool arrays, int dir_bits,
                          ResolveOut &out, hipStream_t s);
 hipError_t warm_resolve();
+// The written (key, value) table of a value history, shared with the
+// list-append entry: tk / tv sorted, tab_op = the write op | kRvFin when it is
+// its txn's last write of the key, tab_txn its txn, and the directory
+// rv_find (hsc_table_dev.h) searches through.  Uses r's sort rows, fin,
+// tab_*, dir and scratch (kept >= min_scratch bytes); r.fin holds a byte per
+// op, r.words_dev the resolve entry's words (>= 256 bytes); words[3] is set on
+// a duplicated (key, value).  wpos: the exclusive scan of the write flags.
+struct ValueTable {
+    size_t nw, cap;
+    const uint64_t *tk, *tv, *tab_op;
+    const uint32_t *tab_txn, *dir;
+    int dir_bits;
+};
+hipError_t value_table_build(size_t n, size_t nw, const uint32_t *txn, const uint64_t *key, const uint8_t *isw,
+                             const uint64_t *val, const uint32_t *wpos, ResolveBufs &r, int dir_bits,
+                             size_t min_scratch, uint32_t *words, ValueTable *vt, hipStream_t s);
+// Stable sort of n rows of two words (w[i], w[cap + i]) with a u64 payload,
+// through r's gid / words2 / pay2 / k0 / k1 / scratch (sized by the caller as
+// value_table_build does); the sorted rows end in *ws / *ps.
+hipError_t sort_rows2(size_t n, size_t cap, ResolveBufs &r, uint64_t *w, uint64_t *pay, bool *ran_packed,
+                      const uint64_t **ws, const uint64_t **ps, hipStream_t s);
+// List-append histories (hsc_lists.hip): the version order of
+// every key from its longest read, the read flags, the committed set and the
+// ww / wr / rw edge rows in cid space, left on the device in buffers of their
+// own for a graph_build through GraphInput::x_rows (~0 rows are holes).
+struct ListBufs {
+    ResolveBufs t;  // the append table, the sorts' rows and scratch
+    DBuf in_txn, in_key, in_isw, in_val, in_off, in_elems, in_status;  // the uploaded history
+    DBuf f0, f1, f2, f3;                         // flags / scans (per op, per read, per spine element)
+    DBuf rd_rows, rd_pay;                        // the reads' sort rows
+    DBuf rk, incompat, rflag;                    // per op: key rank, prefix mismatch, flags
+    DBuf sp_op, sp_len, sp_base, inck;           // per key rank
+    DBuf s_row, first, chain_w, chain_q;         // per spine element / table row / chain entry
+    DBuf level, fate, cid, txn_of, plane, txn_g1;  // per txn
+    DBuf words_dev, list_op, list_flag;
+    DBuf x_rows, x_type;                         // the edge rows
+    size_t n_rows = 0;     // edge rows (holes included)
+    uint32_t nc = 0;       // committed txns
+    bool valid = false;    // a list resolve succeeded and its rows are in place
+    void release_all();
+};
+struct ListIn {  // host pointers
+    size_t nops;
+    uint32_t ntxn;
+    const uint32_t *txn;
+    const uint64_t *key;
+    const uint8_t *is_write;
+    const uint64_t *value, *list_off, *elems;
+    const uint8_t *status;
+};
+struct ListOut {  // host results (hsc_lresolved points into them)
+    std::vector<uint8_t> fate, txn_g1, rflag, listed_flag;
+    std::vector<uint32_t> cid, txn_of_cid;
+    std::vector<uint64_t> listed_op, spine_op;
+    uint32_t ncommitted, recovered, aborted, dropped, g1a_txns, g1b_txns, n_listed, keys, incompatible_keys;
+    uint64_t appends, reads, elements, spine_elements, chain_entries, ww, wr, rw, g1a_reads, g1b_reads,
+        dangling_reads, duplicate_reads, incompatible_reads, internal_reads, unobserved_appends;
+    int bad;  // hipErrorInvalidValue: 1 txn >= ntxn, 2 list_off not ascending, 4 a status > 2, 8 a duplicated append
+};
+hipError_t graph_resolve_lists(const ListIn &in, ListBufs &l, bool arrays, ListOut &out, hipStream_t s);
+hipError_t warm_lists();
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {

@@ -35,17 +35,15 @@
 //             the listed reads compacted up to the cap
 #include <algorithm>
 
-#include "hsc_device.h"
 #include "hsc_internal.h"
+#include "hsc_table_dev.h"
 
 namespace hsc {
 
 namespace {
 
-constexpr int kRvThreads = 256;
 constexpr uint32_t kRvInitTxn = 0xFFFFFFFFu, kRvNoTxn = 0xFFFFFFFEu;
 constexpr uint64_t kRvNoOp = ~0ull;
-constexpr uint64_t kRvFin = 1ull << 63;
 constexpr int kRvSweepsPerTrip = 4;
 constexpr int kRvMaxDirBits = 26;  // the key directory's buckets (256 MiB of u32)
 // device words: [0..3] the input's error words, [4..7] a round trip's change
@@ -54,28 +52,6 @@ constexpr int kRvBadTxn = 0, kRvBadInit = 1, kRvBadStatus = 2, kRvDup = 3, kRvCh
 enum { kCtG1a, kCtG1b, kCtDangling, kCtInternal, kCtRecovered, kCtAborted, kCtDropped, kCtG1aTxns, kCtG1bTxns, kCtN };
 
 inline unsigned rv_blocks(size_t n) { return (unsigned)((n + kRvThreads - 1) / kRvThreads); }
-
-// Sums v[q] over the workgroup and adds every sum that is not zero to dst[q]
-// (every thread of the workgroup calls this).
-template <int N>
-__device__ __forceinline__ void block_add(uint32_t (&v)[N], unsigned long long *dst, uint32_t (*lds)[N])
-{
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        uint32_t x = v[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        if (lane == 0) lds[wid][q] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        uint32_t t = 0;
-#pragma unroll
-        for (int w = 0; w < kRvThreads / 64; ++w) t += lds[w][threadIdx.x];
-        if (t) atomicAdd(dst + threadIdx.x, (unsigned long long)t);
-    }
-}
 
 __global__ __launch_bounds__(kRvThreads) void k_rv_check(size_t nops, uint32_t ntxn, const uint32_t *txn,
                                                          const uint8_t *isw, const uint64_t *value,
@@ -143,16 +119,6 @@ __global__ __launch_bounds__(kRvThreads) void k_rv_table(size_t nw, const uint64
     if (j + 1 < nw && b[j] == b[j + 1] && b[cap + j] == b[cap + j + 1]) words[kRvDup] = 1;
 }
 
-// bucket of key k over [kmin, kmin + span]: (k - kmin) >> shift, below 2^D
-// (shift = 64: one bucket over a span of 64 bits)
-__device__ __forceinline__ int rv_dir_shift(uint64_t span, int D)
-{
-    const int bits = span ? 64 - __clzll((long long)span) : 0;
-    return bits > D ? bits - D : 0;
-}
-__device__ __forceinline__ uint64_t rv_shr(uint64_t x, int shift) { return shift >= 64 ? 0 : x >> shift; }
-__device__ __forceinline__ uint64_t rv_shl(uint64_t x, int shift) { return shift >= 64 ? 0 : x << shift; }
-
 __global__ __launch_bounds__(kRvThreads) void k_rv_dir(size_t nw, const uint64_t *tk, int D, uint32_t *dir)
 {
     const uint32_t q = blockIdx.x * kRvThreads + threadIdx.x, nb = 1u << D;
@@ -191,26 +157,8 @@ __global__ __launch_bounds__(kRvThreads) void k_rv_resolve(size_t nops, size_t n
     const uint64_t v = value[i];
     if (!isw[i] && v != HSC_VAL_INIT) {
         const uint64_t k = key[i];
-        size_t lo = 0, hi = 0;
-        if (nw) {
-            const uint64_t kmin = tk[0], span = tk[nw - 1] - kmin;
-            if (k >= kmin && k - kmin <= span) {
-                const uint32_t b = (uint32_t)rv_shr(k - kmin, rv_dir_shift(span, D));
-                lo = dir[b];
-                hi = dir[b + 1];
-            }
-        }
-        const size_t end = hi;
-        while (lo < hi) {  // the bucket's first row >= (k, v)
-            const size_t mid = lo + ((hi - lo) >> 1);
-            const uint64_t mk = tk[mid];
-            const bool less = mk < k || (mk == k && tv[mid] < v);
-            if (less)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        if (lo < end && tk[lo] == k && tv[lo] == v) {
+        const size_t lo = rv_find(nw, tk, tv, D, dir, k, v);
+        if (lo < nw) {
             const uint64_t e = tab_op[lo];
             const uint32_t w = tab_txn[lo];
             oo = e & ~kRvFin;
@@ -381,8 +329,8 @@ void ResolveBufs::release_all()
 // Stable sort of n rows of two words (w[i], w[cap + i]) with the u64 payload:
 // as packed single words when the rows' varying bits and a row index fit 64
 // bits, by whole rows otherwise.  The sorted rows end in *ws / *ps.
-static hipError_t sort_rows2(size_t n, size_t cap, ResolveBufs &r, uint64_t *w, uint64_t *pay, bool *ran_packed,
-                             const uint64_t **ws, const uint64_t **ps, hipStream_t s)
+hipError_t sort_rows2(size_t n, size_t cap, ResolveBufs &r, uint64_t *w, uint64_t *pay, bool *ran_packed,
+                      const uint64_t **ws, const uint64_t **ps, hipStream_t s)
 {
     *ran_packed = false;
     *ws = w;
@@ -412,6 +360,67 @@ static hipError_t sort_rows2(size_t n, size_t cap, ResolveBufs &r, uint64_t *w, 
         *ws = w2;
         *ps = pay2;
     }
+    return hipSuccess;
+}
+
+// The written (key, value) table of a value history (see the passes above):
+// finality, the table sorted by (key, value) -- a duplicate sets
+// words[kRvDup] -- and its key directory.  wpos: the exclusive scan of the
+// write flags; min_scratch: bytes r.scratch keeps for the caller's scans.
+hipError_t value_table_build(size_t n, size_t nw, const uint32_t *txn, const uint64_t *key, const uint8_t *isw,
+                             const uint64_t *val, const uint32_t *wpos, ResolveBufs &r, int dir_bits,
+                             size_t min_scratch, uint32_t *words, ValueTable *vt, hipStream_t s)
+{
+    const size_t cap = std::max<size_t>(nw, 1);
+    const uint64_t *tk = nullptr;
+    r.sort_path = 0;
+    if (nw) {
+        CK(r.words.ensure(8 * 4 * cap));  // rows a, then rows b
+        CK(r.words2.ensure(8 * 2 * cap));
+        CK(r.pay.ensure(8 * 2 * cap));
+        CK(r.pay2.ensure(8 * cap));
+        CK(r.gid.ensure(4 * cap));
+        CK(r.gid2.ensure(4 * cap));
+        CK(r.k0.ensure(8 * cap));
+        CK(r.k1.ensure(8 * cap));
+        CK(r.tab_op.ensure(8 * cap));
+        CK(r.tab_txn.ensure(4 * cap));
+        CK(r.scratch.ensure(std::max(std::max(radix_scratch_bytes(nw, 2), packed_scratch_bytes(nw)),
+                                     min_scratch)));
+        uint64_t *a = r.words.as<uint64_t>(), *b = a + 2 * cap;
+        uint64_t *apay = r.pay.as<uint64_t>(), *bpay = apay + cap;
+        k_rv_place<<<rv_blocks(n), kRvThreads, 0, s>>>(n, txn, key, isw, val, wpos, cap, a, apay, b, bpay);
+        CK(hipGetLastError());
+        const uint64_t *ws, *ps;
+        bool pk = false;
+        CK(sort_rows2(nw, cap, r, a, apay, &pk, &ws, &ps, s));
+        r.sort_path |= pk ? 2 : 0;
+        k_rv_final<<<rv_blocks(nw), kRvThreads, 0, s>>>(nw, ws, cap, ps, r.fin.as<uint8_t>());
+        CK(hipGetLastError());
+        CK(sort_rows2(nw, cap, r, b, bpay, &pk, &ws, &ps, s));
+        r.sort_path |= pk ? 1 : 0;
+        k_rv_table<<<rv_blocks(nw), kRvThreads, 0, s>>>(nw, ws, cap, ps, txn, r.fin.as<uint8_t>(),
+                                                        r.tab_op.as<uint64_t>(), r.tab_txn.as<uint32_t>(), words);
+        CK(hipGetLastError());
+        tk = ws;
+        // the key directory: about 8 rows a bucket
+        if (dir_bits < 0) {
+            dir_bits = 0;
+            while (dir_bits < kRvMaxDirBits && ((size_t)8 << dir_bits) < nw) ++dir_bits;
+        }
+        dir_bits = std::min(dir_bits, kRvMaxDirBits);
+        CK(r.dir.ensure(4 * (((size_t)1 << dir_bits) + 1)));
+        k_rv_dir<<<rv_blocks(((size_t)1 << dir_bits) + 1), kRvThreads, 0, s>>>(nw, tk, dir_bits, r.dir.as<uint32_t>());
+        CK(hipGetLastError());
+    }
+    vt->nw = nw;
+    vt->cap = cap;
+    vt->tk = tk;
+    vt->tv = tk ? tk + cap : nullptr;
+    vt->tab_op = r.tab_op.as<uint64_t>();
+    vt->tab_txn = r.tab_txn.as<uint32_t>();
+    vt->dir = r.dir.as<uint32_t>();
+    vt->dir_bits = std::max(dir_bits, 0);
     return hipSuccess;
 }
 
@@ -482,47 +491,12 @@ hipError_t graph_resolve(const ResolveIn &in, ResolveBufs &r, bool arrays, int d
     o.writes = nw;
     o.reads = n - nw;
     // finality and the lookup table
-    const size_t cap = std::max<size_t>(nw, 1);
-    const uint64_t *tk = nullptr;
-    if (nw) {
-        CK(r.words.ensure(8 * 4 * cap));  // rows a, then rows b
-        CK(r.words2.ensure(8 * 2 * cap));
-        CK(r.pay.ensure(8 * 2 * cap));
-        CK(r.pay2.ensure(8 * cap));
-        CK(r.gid.ensure(4 * cap));
-        CK(r.gid2.ensure(4 * cap));
-        CK(r.k0.ensure(8 * cap));
-        CK(r.k1.ensure(8 * cap));
-        CK(r.tab_op.ensure(8 * cap));
-        CK(r.tab_txn.ensure(4 * cap));
-        CK(r.scratch.ensure(std::max(std::max(radix_scratch_bytes(nw, 2), packed_scratch_bytes(nw)),
-                                     scan_scratch_bytes(std::max(n1, t1) + 1) + 64)));
-        uint64_t *a = r.words.as<uint64_t>(), *b = a + 2 * cap;
-        uint64_t *apay = r.pay.as<uint64_t>(), *bpay = apay + cap;
-        k_rv_place<<<rv_blocks(n), kRvThreads, 0, s>>>(n, txn, key, isw, val, f0, cap, a, apay, b, bpay);
-        CK(hipGetLastError());
-        const uint64_t *ws, *ps;
-        bool pk = false;
-        CK(sort_rows2(nw, cap, r, a, apay, &pk, &ws, &ps, s));
-        r.sort_path |= pk ? 2 : 0;
-        k_rv_final<<<rv_blocks(nw), kRvThreads, 0, s>>>(nw, ws, cap, ps, r.fin.as<uint8_t>());
-        CK(hipGetLastError());
-        CK(sort_rows2(nw, cap, r, b, bpay, &pk, &ws, &ps, s));
-        r.sort_path |= pk ? 1 : 0;
-        k_rv_table<<<rv_blocks(nw), kRvThreads, 0, s>>>(nw, ws, cap, ps, txn, r.fin.as<uint8_t>(),
-                                                        r.tab_op.as<uint64_t>(), r.tab_txn.as<uint32_t>(), words);
-        CK(hipGetLastError());
-        tk = ws;
-        // the key directory: about 8 rows a bucket
-        if (dir_bits < 0) {
-            dir_bits = 0;
-            while (dir_bits < kRvMaxDirBits && ((size_t)8 << dir_bits) < nw) ++dir_bits;
-        }
-        dir_bits = std::min(dir_bits, kRvMaxDirBits);
-        CK(r.dir.ensure(4 * (((size_t)1 << dir_bits) + 1)));
-        k_rv_dir<<<rv_blocks(((size_t)1 << dir_bits) + 1), kRvThreads, 0, s>>>(nw, tk, dir_bits, r.dir.as<uint32_t>());
-        CK(hipGetLastError());
-    }
+    ValueTable vt{};
+    CK(value_table_build(n, nw, txn, key, isw, val, f0, r, dir_bits, scan_scratch_bytes(std::max(n1, t1) + 1) + 64,
+                         words, &vt, s));
+    const size_t cap = vt.cap;
+    const uint64_t *tk = vt.tk;
+    dir_bits = vt.dir_bits;
     uint64_t *obs_op = r.obs_op.as<uint64_t>();
     uint32_t *obs_txn = r.obs_txn.as<uint32_t>();
     uint8_t *rflag = r.rflag.as<uint8_t>();

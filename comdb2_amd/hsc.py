@@ -161,6 +161,36 @@ class Resolved(C.Structure):
                 ("sweeps", C.c_uint32), ("ms", C.c_float)]
 
 
+# hsc_dep_graph_resolve_lists: the list-append read flags beside RD_*
+LRD_INCOMPATIBLE, LRD_DUPLICATE = 16, 32
+
+
+class _LHistory(C.Structure):
+    _fields_ = [("nops", C.c_size_t), ("ntxn", C.c_uint32), ("txn", _p), ("key", _p),
+                ("is_write", _p), ("value", _p), ("list_off", _p), ("elems", _p), ("status", _p)]
+
+
+class LResolved(C.Structure):
+    """hsc_lresolved: the arrays are host memory of the context."""
+    _fields_ = [("nops", C.c_size_t), ("ntxn", C.c_uint32), ("ncommitted", C.c_uint32),
+                ("recovered", C.c_uint32), ("aborted", C.c_uint32), ("dropped", C.c_uint32),
+                ("appends", C.c_uint64), ("reads", C.c_uint64), ("elements", C.c_uint64),
+                ("keys", C.c_uint32), ("incompatible_keys", C.c_uint32),
+                ("spine_elements", C.c_uint64), ("chain_entries", C.c_uint64), ("ww", C.c_uint64),
+                ("wr", C.c_uint64), ("rw", C.c_uint64), ("g1a_reads", C.c_uint64), ("g1b_reads", C.c_uint64),
+                ("dangling_reads", C.c_uint64), ("duplicate_reads", C.c_uint64),
+                ("incompatible_reads", C.c_uint64), ("internal_reads", C.c_uint64),
+                ("unobserved_appends", C.c_uint64), ("g1a_txns", C.c_uint32), ("g1b_txns", C.c_uint32),
+                ("fate", _p), ("cid", _p), ("txn_of_cid", _p), ("txn_g1", _p), ("n_listed", C.c_uint32),
+                ("listed_op", _p), ("listed_flag", _p), ("rflag", _p), ("spine_op", _p), ("ms", C.c_float)]
+
+
+LRESOLVED_COUNTERS = ("nops", "ntxn", "ncommitted", "recovered", "aborted", "dropped", "appends", "reads",
+                      "elements", "keys", "incompatible_keys", "spine_elements", "chain_entries", "ww", "wr",
+                      "rw", "g1a_reads", "g1b_reads", "dangling_reads", "duplicate_reads", "incompatible_reads",
+                      "internal_reads", "unobserved_appends", "g1a_txns", "g1b_txns", "n_listed")
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -235,6 +265,7 @@ EXPORTS = [
     "hsc_dep_graph_build", "hsc_dep_graph_stage_rw_pairs", "hsc_dep_graph_stage_realtime", "hsc_dep_graph_scc_built", "hsc_dep_graph_build_device", "hsc_dep_graph_cover", "hsc_dep_graph_cut", "hsc_dep_graph_scc_cut",
     "hsc_dep_graph_anomalies", "hsc_dep_graph_si",
     "hsc_dep_graph_resolve", "hsc_dep_graph_build_resolved", "hsc_dep_graph_resolve_sort_path",
+    "hsc_dep_graph_resolve_lists", "hsc_dep_graph_build_lists",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -327,6 +358,8 @@ def load() -> C.CDLL:
         "hsc_dep_graph_resolve": (C.c_int, [_p, C.POINTER(_VHistory), C.c_uint, C.POINTER(Resolved)]),
         "hsc_dep_graph_build_resolved": (C.c_int, [_p, C.c_int, C.POINTER(GraphStats)]),
         "hsc_dep_graph_resolve_sort_path": (C.c_int, [_p]),
+        "hsc_dep_graph_resolve_lists": (C.c_int, [_p, C.POINTER(_LHistory), C.c_uint, C.POINTER(LResolved)]),
+        "hsc_dep_graph_build_lists": (C.c_int, [_p, C.c_int, C.POINTER(GraphStats)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
         "hsc_window_ingest_raw": (C.c_int, [_p, C.POINTER(_RawLog)]),
@@ -1233,6 +1266,53 @@ class Validator:
         flags = (1 if full else 0) | (2 if no_rw else 0)
         self._chk(self.lib.hsc_dep_graph_build_resolved(self.ctx, flags, C.byref(st)),
                   "hsc_dep_graph_build_resolved")
+        return st.as_dict()
+
+    def graph_resolve_lists(self, lh, arrays: bool = True) -> dict:
+        """The version orders of a list-append history (workloads.ListHistory;
+        hsc_dep_graph_resolve_lists): every key's spine (its longest read by an
+        OK txn), the read flags against it (RD_* and LRD_INCOMPATIBLE /
+        LRD_DUPLICATE), which UNKNOWN txns committed, and the ww / wr / rw
+        edge rows left on the device for graph_build_lists.  No premise on
+        txn ids.  Copies of every field; without ``arrays`` rflag and spine_op
+        are None.  (The two list entries are named outside the ``dep_graph_``
+        prefix: tests/test_gpu_graph_entries.py keeps an inventory of that
+        prefix's methods, and tests/test_gpu_lists.py covers these two.)"""
+        cols = [np.ascontiguousarray(lh.txn, np.uint32), np.ascontiguousarray(lh.key, np.uint64),
+                np.ascontiguousarray(lh.is_write, np.uint8), np.ascontiguousarray(lh.value, np.uint64),
+                np.ascontiguousarray(lh.list_off, np.uint64), np.ascontiguousarray(lh.elems, np.uint64),
+                np.ascontiguousarray(lh.status, np.uint8)]
+        n, ntxn = len(cols[0]), int(lh.ntxn)
+        if not (len(cols[1]) == len(cols[2]) == len(cols[3]) == n) or len(cols[4]) != n + 1 or \
+                len(cols[6]) != ntxn:
+            raise ValueError("list history: the per-op arrays must share a length, list_off hold one more "
+                             "and status hold ntxn")
+        if len(cols[5]) < int(cols[4][-1]):
+            raise ValueError("list history: elems is shorter than list_off[nops]")
+        hs = _LHistory(n, ntxn, *[c.ctypes.data for c in cols])
+        a = LResolved()
+        self._chk(self.lib.hsc_dep_graph_resolve_lists(self.ctx, C.byref(hs), RESOLVE_ARRAYS if arrays else 0,
+                                                       C.byref(a)), "hsc_dep_graph_resolve_lists")
+        arr = _copy_out
+        out = {k: getattr(a, k) for k in LRESOLVED_COUNTERS + ("ms",)}
+        out["fate"] = arr(a.fate, ntxn, np.uint8)
+        out["cid"] = arr(a.cid, ntxn, np.uint32)
+        out["txn_of_cid"] = arr(a.txn_of_cid, a.ncommitted, np.uint32)
+        out["txn_g1"] = arr(a.txn_g1, ntxn, np.uint8)
+        out["listed_op"] = arr(a.listed_op, a.n_listed, np.uint64)
+        out["listed_flag"] = arr(a.listed_flag, a.n_listed, np.uint8)
+        out["rflag"] = arr(a.rflag, n, np.uint8) if arrays else None
+        out["spine_op"] = arr(a.spine_op, a.keys, np.uint64) if arrays else None
+        return out
+
+    def graph_build_lists(self, full: bool = True) -> dict:
+        """The build of the last graph_resolve_lists' ncommitted txns (ids
+        = cid) from its edge rows; a staged real-time order joins, staged rw
+        pairs are refused (hsc_dep_graph_build_lists).  dep_graph_edges,
+        dep_graph_scc_built, dep_graph_anomalies and dep_graph_si run on it."""
+        st = GraphStats()
+        self._chk(self.lib.hsc_dep_graph_build_lists(self.ctx, 1 if full else 0, C.byref(st)),
+                  "hsc_dep_graph_build_lists")
         return st.as_dict()
 
     def probe_device(self, batch: ProbeBatch) -> None:

@@ -63,6 +63,15 @@ committed, and run the analyses of ``check_edn`` on the committed part.
 dirty-reads workload (linearizable/jepsen/src/comdb2/core.clj:320-353,
 :492-523: "a failed transaction whose value became visible to some read").
 Internal consistency (a txn reading its own earlier write) is not checked.
+
+Both conversions above take completion order for commit order, which a Jepsen
+history does not carry.  A list-append history needs no such premise:
+:func:`lhistory_from_append_edn` reads Elle's ``[:append k v]`` / ``[:r k [v
+...]]`` form into a :class:`workloads.ListHistory`, and
+:func:`check_append_edn` has the GPU recover every key's version order from
+its longest read (``Validator.graph_resolve_lists``), report G1a / G1b,
+incompatible orders and duplicated elements, and run the same analyses on the
+edges that order gives.
 """
 from __future__ import annotations
 
@@ -72,7 +81,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .workloads import TXN_ABORTED, TXN_OK, TXN_UNKNOWN, VAL_INIT, History, ValueHistory
+from .workloads import TXN_ABORTED, TXN_OK, TXN_UNKNOWN, VAL_INIT, History, ListHistory, ValueHistory
 
 # ---------------------------------------------------------------------------
 # EDN (the subset the histories use: maps, vectors, keywords, integers, nil,
@@ -644,6 +653,147 @@ def check_txn_edn(validator, text: str, witness: bool = True, realtime: bool = F
     return report
 
 
+# ---------------------------------------------------------------------------
+# list-append histories: the version order comes from the reads
+# ---------------------------------------------------------------------------
+@dataclasses.dataclass
+class AppendOps:
+    """Every attempted txn of a list-append history, in txn id order (the
+    fields of :class:`TxnOps`, the history a :class:`ListHistory`)."""
+    lhistory: ListHistory
+    ok: int
+    failed: int
+    info: int
+    unpaired: int
+    txn_ops: List[dict]
+    invoke: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint64))
+    complete: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.uint64))
+    g2_keys: Dict[int, int] = dataclasses.field(default_factory=dict)  # (anomaly_report reads it: none here)
+
+
+def lhistory_from_append_edn(text: str) -> AppendOps:
+    """Elle's list-append histories, ``{:f :txn :value [[:append k v]
+    [:r k [v ...]] ...]}`` (keys and elements non-negative integers), as a
+    list history of every attempted txn: ``:ok`` is TXN_OK, ``:fail``
+    TXN_ABORTED, ``:info`` or an invoke without a completion TXN_UNKNOWN.  A
+    ``nil`` or ``[]`` read is the empty list.  An op that did not complete
+    ``:ok`` gives its appends from the invoke and no reads.  Txn ids follow
+    :func:`vhistory_from_txn_edn`'s order; nothing downstream relies on it."""
+    att = _attempts(text, (":txn",))
+    ops = []
+    for t, (inv, op, st, _, _) in enumerate(att):
+        src = op if st == TXN_OK else (inv if ":value" in inv else (op or {}))
+        for m in src.get(":value") or ():
+            f, k, v = m
+            if f == ":append":
+                if v is None:
+                    raise ValueError("an :append micro-op without an element")
+                ops.append((t, int(k), int(v)))
+            elif f == ":r":
+                if st == TXN_OK:
+                    ops.append((t, int(k), [int(x) for x in (v or ())]))
+            else:
+                raise ValueError(f"unknown micro-op {f!r}")
+    status = np.array([a[2] for a in att], np.uint8)
+    invoke, complete = _attempt_intervals(att)
+    return AppendOps(ListHistory.from_ops(ops, status), int((status == TXN_OK).sum()),
+                     int((status == TXN_ABORTED).sum()),
+                     sum(1 for a in att if a[2] == TXN_UNKNOWN and a[1] is not None),
+                     sum(1 for a in att if a[1] is None), [a[1] if a[1] is not None else a[0] for a in att],
+                     invoke, complete)
+
+
+_LRESOLVE_STATS = ("nops", "ntxn", "ncommitted", "recovered", "aborted", "dropped", "appends", "reads", "elements",
+                   "keys", "incompatible_keys", "spine_elements", "chain_entries", "ww", "wr", "rw", "g1a_reads",
+                   "g1b_reads", "dangling_reads", "duplicate_reads", "incompatible_reads", "internal_reads",
+                   "unobserved_appends", "g1a_txns", "g1b_txns", "n_listed", "ms")
+_LRD_INCOMPATIBLE, _LRD_DUPLICATE = 16, 32  # HSC_LRD_*
+
+
+def listed_list_reads(lh: ListHistory, res: dict) -> dict:
+    """``aborted_reads`` / ``intermediate_reads`` / ``dangling_reads`` /
+    ``duplicate_reads`` / ``incompatible_reads`` of a graph_resolve_lists
+    dict: one entry {reader, key, reader_op, list} per listed read carrying the
+    flag, and the exact ``*_count`` of each (the lists stop at the entry's
+    cap)."""
+    names = ((_RD_ABORTED, "aborted_reads"), (_RD_INTERMEDIATE, "intermediate_reads"),
+             (_RD_DANGLING, "dangling_reads"), (_LRD_DUPLICATE, "duplicate_reads"),
+             (_LRD_INCOMPATIBLE, "incompatible_reads"))
+    out = {name: [] for _, name in names}
+    for i, f in zip(res["listed_op"], res["listed_flag"]):
+        i, f = int(i), int(f)
+        e = {"reader": int(lh.txn[i]), "key": int(lh.key[i]), "reader_op": i,
+             "list": [int(x) for x in lh.elems[int(lh.list_off[i]):int(lh.list_off[i + 1])]]}
+        for bit, name in names:
+            if f & bit:
+                out[name].append(e)
+    out["aborted_read_count"] = int(res["g1a_reads"])
+    out["intermediate_read_count"] = int(res["g1b_reads"])
+    out["dangling_read_count"] = int(res["dangling_reads"])
+    out["duplicate_read_count"] = int(res["duplicate_reads"])
+    out["incompatible_read_count"] = int(res["incompatible_reads"])
+    return out
+
+
+def check_append_edn(validator, text: str, witness: bool = True, realtime: bool = False,
+                     isolation: bool = False) -> dict:
+    """A list-append history through the GPU with no premise on commit order:
+    the version order of every key is its longest read
+    (``Validator.graph_resolve_lists``), the graph is built from the edges
+    that order gives (``graph_build_lists``), and the analyses of
+    :func:`check_edn` run on it.  Where :func:`check_txn_edn` must take
+    completion order for version order -- and reports a false cycle, or misses
+    one, when two concurrent writers of a key complete in the other order --
+    this check reads the order the database applied from the data.
+
+    The report has :func:`check_txn_edn`'s keys, the txns of ``cycles`` /
+    ``si_cycles`` / ``realtime_cycles`` and their ``label`` mapped back to
+    attempted-txn ids, plus :func:`listed_list_reads`' keys (``duplicate_reads``
+    and ``incompatible_reads`` with their counts among them).
+    ``anomaly_types`` gains "G1a", "G1b", "incompatible-order" (a read that is
+    not a prefix of its key's longest read), "duplicate-elements" and "G0":
+    a component whose witness cycle is made of ww edges only (its entry in
+    ``cycles`` keeps the class ``type`` "G1c" and has ``g0`` True).  G0 is a
+    lower bound: one witness is looked at per component, so a component may
+    hold a ww-only cycle its witness does not show, and without ``witness``
+    none is named.  ``valid`` = no cycle and none of the above; ``levels``
+    (with ``isolation``) gains ``read_committed``.  ``resolve`` holds the
+    entry's stats, ``history`` the :class:`AppendOps`.  A dangling read is
+    listed and counted, and does not by itself make the history invalid, as
+    in :func:`check_txn_edn`.  Internal consistency is not checked."""
+    tx = lhistory_from_append_edn(text)
+    res = validator.graph_resolve_lists(tx.lhistory, arrays=True)
+    toc = [int(t) for t in res["txn_of_cid"]]
+    sel = np.asarray(toc, np.int64)
+    committed = AppendOps(tx.lhistory, tx.ok, tx.failed, tx.info, tx.unpaired, [tx.txn_ops[t] for t in toc],
+                          tx.invoke[sel], tx.complete[sel])
+    report = _check_built(validator, committed, lambda: validator.graph_build_lists(full=True),
+                          len(toc), witness, realtime, isolation)
+    for name in ("cycles", "si_cycles", "realtime_cycles"):
+        for c in report.get(name, ()):
+            c["txns"] = [toc[t] for t in c["txns"]]
+            c["label"] = toc[c["label"]]
+    g0 = False
+    for c in report["cycles"]:
+        c["g0"] = bool(c["edge_types"]) and all(t == "ww" for t in c["edge_types"])
+        g0 = g0 or c["g0"]
+    report["history"] = tx
+    report.update(listed_list_reads(tx.lhistory, res))
+    extra = {name for name, k in (("G1a", "g1a_reads"), ("G1b", "g1b_reads"),
+                                  ("incompatible-order", "incompatible_reads"),
+                                  ("duplicate-elements", "duplicate_reads")) if int(res[k]) > 0}
+    if g0:
+        extra.add("G0")
+    report["anomaly_types"] = sorted(set(report["anomaly_types"]) | extra)
+    report["valid"] = bool(report["valid"]) and not extra
+    if isolation:
+        g1 = int(res["g1a_reads"]) > 0 or int(res["g1b_reads"]) > 0
+        report["levels"]["read_committed"] = not g1 and bool(report["levels"]["g1c_free"])
+    report["resolve"] = {k: res[k] for k in _LRESOLVE_STATS if k in res}
+    report["resolve_arrays"] = {k: res[k] for k in ("fate", "cid", "txn_of_cid", "txn_g1")}
+    return report
+
+
 # ---- the reference's dirty-reads workload (core.clj:320-353, :492-523) ------
 @dataclasses.dataclass
 class DirtyOps:
@@ -864,6 +1014,130 @@ def txn_history_edn(seed: int, n_txns: int = 2000, n_procs: int = 8, n_keys: int
             busy[p] = now
             p_new = n_procs + len(lines)  # a crashed process never comes back
             lines[-1] = (inv_t, lines[-1][1], lines[-1][2].replace(f":process {p} ", f":process {p_new} "))
+    lines.sort()
+    return "\n".join(l for _, _, l in lines) + "\n", inj
+
+
+def append_history_edn(seed: int, n_txns: int = 2000, n_procs: int = 24, n_keys: int = 50, fail: float = 0.05,
+                       info: float = 0.03, lag: int = 200, dirty: float = 0.02, intermediate: float = 0.3,
+                       dangling: float = 0.002, duplicate: float = 0.002, incompatible: float = 0.002,
+                       cycles: bool = True) -> Tuple[str, dict]:
+    """A list-append history (``:f :txn``, Elle's ``:append`` / ``:r``) of a
+    serial execution with overlapping intervals: txn i takes effect at an
+    instant inside [invoke, completion], and completes up to ``lag`` later, so
+    completion order often differs from the order the appends were applied in.
+    ``fail`` of the txns complete :fail (not applied), ``info`` complete :info
+    or never (applied half the time).  Switches, each 0 / False for a clean
+    history: ``dirty`` -- a failed txn's appends are applied all the same
+    (G1a); ``intermediate`` -- of the txns that append twice to a key, the
+    share whose state between the two is read by a concurrent txn (G1b);
+    ``dangling`` / ``duplicate`` -- per append, an element nobody appended / a
+    repeat of an element slips into the list; ``incompatible`` -- per read of
+    two or more elements, the last two come back swapped; ``cycles`` -- one
+    G0, G1c, G-single and G2 (write skew) on keys of their own at the end.
+    With every switch off the history is strict serializable.  Returns (EDN
+    text, the number of injections made per switch)."""
+    rng = np.random.default_rng(seed)
+    state: Dict[int, List[int]] = {}
+    lines: List[Tuple[int, int, str]] = []
+    busy = np.zeros(n_procs, np.int64)
+    now, nextv, extra_proc = 1000, 1, n_procs
+    inj = {"dirty": 0, "intermediate": 0, "dangling": 0, "duplicate": 0, "incompatible": 0, "cycles": 0}
+
+    def fmt(ms, blank):
+        def one(f, k, v):
+            if f == ":append":
+                return f"[:append {k} {v}]"
+            return f"[:r {k} nil]" if blank else f"[:r {k} [{' '.join(str(x) for x in v)}]]"
+        return "[" + " ".join(one(*m) for m in ms) + "]"
+
+    def emit(p, inv_t, end_t, kind, ms):
+        lines.append((inv_t, len(lines), f"{{:type :invoke :f :txn :value {fmt(ms, True)} :process {p} "
+                                         f":time {inv_t}}}"))
+        if end_t is not None:
+            lines.append((end_t, len(lines), f"{{:type {kind} :f :txn :value {fmt(ms, kind != ':ok')} "
+                                             f":process {p} :time {end_t}}}"))
+
+    for _ in range(n_txns):
+        now += int(rng.integers(1, 50))
+        free = np.nonzero(busy < now)[0]
+        if not len(free):
+            now = int(busy.min()) + 1
+            free = np.nonzero(busy < now)[0]
+        p = int(free[int(rng.integers(0, len(free)))])
+        inv_t = max(int(busy[p]) + 1, now - int(rng.integers(0, lag + 1)))
+        end_t = now + int(rng.integers(0, lag + 1))
+        u = rng.random()
+        kind = ":fail" if u < fail else ":info" if u < fail + info else ":ok"
+        applied = kind == ":ok" or (kind == ":info" and rng.random() < 0.5)
+        if kind == ":fail" and rng.random() < dirty:
+            applied = True
+            inj["dirty"] += 1
+        ms, work, between = [], {}, None
+
+        def cur(k):
+            if k not in work:
+                work[k] = list(state.get(k, ()))
+            return work[k]
+
+        for _ in range(int(rng.integers(1, 5))):
+            k = int(rng.integers(0, n_keys))
+            if rng.random() < 0.5:
+                twice = rng.random() < 0.15
+                for q in range(2 if twice else 1):
+                    lst = cur(k)
+                    if rng.random() < dangling:
+                        lst.append(10 ** 9 + nextv)  # nobody's element
+                        inj["dangling"] += 1
+                    if lst and rng.random() < duplicate:
+                        lst.append(lst[int(rng.integers(0, len(lst)))])
+                        inj["duplicate"] += 1
+                    lst.append(nextv)
+                    ms.append((":append", k, nextv))
+                    nextv += 1
+                    if twice and q == 0 and between is None and kind == ":ok" and rng.random() < intermediate:
+                        between = (k, list(lst))
+            else:
+                v = list(cur(k))
+                if len(v) >= 2 and rng.random() < incompatible:
+                    v[-1], v[-2] = v[-2], v[-1]
+                    inj["incompatible"] += 1
+                ms.append((":r", k, v))
+        if applied:
+            state.update(work)
+        if between is not None:  # a concurrent txn saw the list between the two appends
+            emit(extra_proc, now - 1, now + 1, ":ok", [(":r", between[0], between[1])])
+            extra_proc += 1
+            inj["intermediate"] += 1
+        if kind != ":info" or rng.random() < 0.5:
+            emit(p, inv_t, end_t, kind, ms)
+            busy[p] = end_t
+        else:  # never completes: a crashed process does not come back
+            emit(extra_proc, inv_t, None, kind, ms)
+            extra_proc += 1
+    if cycles:
+        t0 = max([now] + [t for t, _, _ in lines]) + 1000
+        k, v = 10 ** 6, nextv
+        gadgets = [
+            # G0: the version orders of two keys disagree
+            [[(":append", k, v), (":append", k + 1, v + 1)], [(":append", k, v + 2), (":append", k + 1, v + 3)],
+             [(":r", k, [v, v + 2]), (":r", k + 1, [v + 3, v + 1])]],
+            # G1c: each read the other's append
+            [[(":append", k + 2, v + 4), (":r", k + 3, [v + 5])], [(":append", k + 3, v + 5), (":r", k + 2, [v + 4])]],
+            # G-single: one of the first txn's two appends seen, the other missed
+            [[(":append", k + 4, v + 6), (":append", k + 5, v + 7)], [(":r", k + 4, [v + 6]), (":r", k + 5, [])],
+             [(":r", k + 5, [v + 7])]],
+            # G2: write skew
+            [[(":r", k + 6, []), (":r", k + 7, []), (":append", k + 6, v + 8)],
+             [(":r", k + 6, []), (":r", k + 7, []), (":append", k + 7, v + 9)],
+             [(":r", k + 6, [v + 8]), (":r", k + 7, [v + 9])]],
+        ]
+        for g in gadgets:
+            for ms in g:
+                emit(extra_proc, t0, t0 + 10, ":ok", ms)
+                extra_proc += 1
+            t0 += 100
+            inj["cycles"] += 1
     lines.sort()
     return "\n".join(l for _, _, l in lines) + "\n", inj
 

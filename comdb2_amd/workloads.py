@@ -506,6 +506,42 @@ class ValueHistory:
         return int(len(self.txn))
 
 
+@dataclasses.dataclass
+class ListHistory:
+    """Micro-ops of every attempted transaction of a list-append history
+    (hsc_lhistory): a write appends ``value`` to its key's list, read op i
+    returned ``elems[list_off[i]:list_off[i + 1]]`` (an append's run is
+    empty).  The ops of one txn stand in program order; appended
+    (key, element) pairs are unique; txn ids may be in any order."""
+    txn: np.ndarray        # uint32[nops]
+    key: np.ndarray        # uint64[nops]
+    is_write: np.ndarray   # uint8[nops] 1 = append
+    value: np.ndarray      # uint64[nops] the appended element (reads: ignored)
+    list_off: np.ndarray   # uint64[nops + 1] ascending
+    elems: np.ndarray      # uint64[list_off[nops]]
+    status: np.ndarray     # uint8[ntxn] TXN_OK / TXN_ABORTED / TXN_UNKNOWN
+    ntxn: int
+
+    @property
+    def nops(self) -> int:
+        return int(len(self.txn))
+
+    @classmethod
+    def from_ops(cls, ops, status) -> "ListHistory":
+        """ops: (txn, key, element) for an append, (txn, key, [elements]) for
+        a read, in array order."""
+        txn, key, isw, val, off, el = [], [], [], [], [0], []
+        for t, k, v in ops:
+            rd = isinstance(v, (list, tuple))
+            txn.append(t), key.append(k), isw.append(0 if rd else 1), val.append(0 if rd else v)
+            if rd:
+                el.extend(v)
+            off.append(len(el))
+        return cls(np.array(txn, np.uint32), np.array(key, np.uint64), np.array(isw, np.uint8),
+                   np.array(val, np.uint64), np.array(off, np.uint64), np.array(el, np.uint64),
+                   np.array(status, np.uint8), len(status))
+
+
 def value_history(h: History, status: Optional[np.ndarray] = None) -> ValueHistory:
     """h in value form: a write's value is its txn + 1, a read's the observed
     txn + 1 (VAL_INIT for the initial version).  Every txn OK unless status

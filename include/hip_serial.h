@@ -845,6 +845,12 @@ int hsc_dep_graph_scc_built(hsc_ctx *ctx, uint32_t *scc_out, hsc_graph_stats *st
  * is made of ww edges alone; an rt edge between completed txns goes up in
  * commit order as well (a completed before b was invoked, so before b
  * completed), so ww and rt edges together make no cycle either.
+ * A build from a list-append history (hsc_dep_graph_build_lists) is the one
+ * exception: its version orders come from the reads, not from txn ids, so its
+ * ww edges may go down in id and a cycle of ww edges alone (G0) can exist.
+ * Such a cycle is an E1 cycle and is classed HSC_ANOM_G1C here; telling G0
+ * apart is left to the caller (jepsen.check_append_edn names it when the
+ * witness cycle is ww only).
  * HSC_ANOM_WITNESS: per component one simple cycle of its class, wit_txn
  * [wit_off[i], wit_off[i + 1]).  Its closing edge last -> first is the lowest
  * edge, in the build's (src, dst) order, that is -- class G1c: an E1 edge
@@ -1026,6 +1032,108 @@ int hsc_dep_graph_build_resolved(hsc_ctx *ctx, int flags, hsc_graph_stats *stats
  * bit 1 the (key, txn) finality rows -- set: as packed single words, clear: by
  * whole rows (or nothing to sort). */
 int hsc_dep_graph_resolve_sort_path(hsc_ctx *ctx);
+/* ---- list-append histories: the version order from the reads --------------
+ * Every graph entry above rests on one premise: txn ids are commit order and a
+ * key's version order is its writers' commit order.  A list-append history
+ * (Elle's main workload) needs no such premise: every write appends a unique
+ * element to its key's list, every read returns the whole list, and the
+ * longest read of a key is that key's version order.  This entry recovers the
+ * version orders on the GPU, flags the reads against them, decides which
+ * indeterminate txns committed and emits the ww / wr / rw edges, which
+ * hsc_dep_graph_build_lists turns into a build every analysis above runs on.
+ * Premises:
+ *   - the ops of one txn stand in program order in the arrays (they need not
+ *     be contiguous);
+ *   - appended (key, element) pairs are unique over the whole history, aborted
+ *     and unknown txns included; the same element on two keys is fine;
+ *   - nothing about txn ids: they may be in any order.
+ * Spine.  S_k, the spine of key k, is the longest list among the reads of k by
+ * HSC_TXN_OK txns; a tie goes to the lowest op index.  Reads by txns of any
+ * other status are ignored throughout (no flags, no edges, not counted in the
+ * flag counters).  A key no OK txn read has an empty spine and no rank; the
+ * keys that have one are ranked in ascending key (keys, spine_op[rank]).
+ * Read flags (reads of OK txns only).  HSC_LRD_INCOMPATIBLE: the list is not a
+ * prefix of S_k (Elle's incompatible-order); such a read gets no other flag
+ * and no edges.  A compatible read of length n takes its other flags from the
+ * first n spine positions:
+ *   HSC_RD_DANGLING      one of them holds an element nobody appended;
+ *   HSC_LRD_DUPLICATE    one of them repeats an earlier position's element;
+ *   HSC_RD_ABORTED       (G1a) one of them was appended by an ABORTED txn;
+ *   HSC_RD_INTERMEDIATE  (G1b) position n - 1 was appended by w != the reader,
+ *                        and that append is not w's last append to k in
+ *                        program order;
+ *   HSC_RD_INTERNAL      counted only (see the wr edge below).
+ * Committed set C: the OK txns plus every UNKNOWN txn that has an append whose
+ * element stands in its key's spine (recovered).  One pass, no sweeps: only OK
+ * txns read.  fate, cid and txn_of_cid are as in hsc_resolved (cid: the dense
+ * rank among C in ascending id); txn_g1[r] bit 1 / bit 2: r has a read flagged
+ * ABORTED / INTERMEDIATE.
+ * Chain of k: the spine positions, in spine order, whose element resolves to
+ * an append, is that element's first occurrence in the spine, and was appended
+ * by a txn in C.  ww edge: the writer of chain[c] -> the writer of
+ * chain[c + 1] where the two differ.
+ * wr / rw edges.  A compatible read by r with c chain entries among its first
+ * n positions gives wr: writer(chain[c - 1]) -> r if c > 0, and rw: r ->
+ * writer(chain[c]) if the chain has such an entry.  An empty read has n = 0
+ * and c = 0: it anti-depends on the first writer.  Self edges are dropped;
+ * internal_reads counts the reads whose chain[c - 1] was written by r itself
+ * (they carry HSC_RD_INTERNAL).  Edges are in cid space.  ww / wr / rw count
+ * the rows emitted, before the build merges parallel edges.
+ * An append by a txn of C whose element stands in no spine has no known
+ * position: it yields no edge and is counted in unobserved_appends.
+ * appends / reads count every op of the history; elements = list_off[nops].
+ * listed_op: up to HSC_RESOLVE_LIST_CAP read ops with a flag other than
+ * INTERNAL, in ascending op index, their flags in listed_flag.
+ * HSC_EINVAL: a NULL argument, txn[i] >= ntxn, a status above 2, a list_off
+ * that is not ascending, a duplicated append, more than 2^31 - 1 ops, txns or
+ * elements.  HSC_EDEVICE: a host-only context.  Empty histories succeed.  The
+ * arrays are host memory owned by the context, never NULL (rflag and spine_op
+ * hold nothing without HSC_RESOLVE_ARRAYS), valid until the next graph call.
+ * The edge rows stay on the device in buffers of their own: a plain
+ * hsc_dep_graph_build does not disturb them, nor they it.  The sharded path
+ * (hsc_multi_graph_scc) has no such entry. */
+#define HSC_LRD_INCOMPATIBLE 16
+#define HSC_LRD_DUPLICATE    32
+typedef struct hsc_lhistory {          /* every attempted txn, host pointers */
+    size_t nops; uint32_t ntxn;
+    const uint32_t *txn;               /* [nops] < ntxn; ids in ANY order */
+    const uint64_t *key;               /* [nops] */
+    const uint8_t  *is_write;          /* [nops] 1 = append */
+    const uint64_t *value;             /* [nops] append: the element; read: ignored */
+    const uint64_t *list_off;          /* [nops+1] ascending; read op i returned
+                                          elems[list_off[i] .. list_off[i+1]); an append's run is empty */
+    const uint64_t *elems;             /* [list_off[nops]] */
+    const uint8_t  *status;            /* [ntxn] HSC_TXN_* */
+} hsc_lhistory;
+typedef struct hsc_lresolved {
+    size_t nops;  uint32_t ntxn, ncommitted, recovered, aborted, dropped;
+    uint64_t appends, reads, elements;
+    uint32_t keys, incompatible_keys;             /* keys with a spine / with an incompatible read */
+    uint64_t spine_elements, chain_entries, ww, wr, rw;
+    uint64_t g1a_reads, g1b_reads, dangling_reads, duplicate_reads, incompatible_reads, internal_reads;
+    uint64_t unobserved_appends;
+    uint32_t g1a_txns, g1b_txns;
+    const uint8_t *fate;         /* [ntxn] 0 committed, 1 aborted, 2 dropped, 3 recovered */
+    const uint32_t *cid;         /* [ntxn] */
+    const uint32_t *txn_of_cid;  /* [ncommitted] */
+    const uint8_t *txn_g1;       /* [ntxn] */
+    uint32_t n_listed;           /* min(cap, flagged reads) */
+    const uint64_t *listed_op;   /* ascending read op index */
+    const uint8_t *listed_flag;  /* its flags */
+    const uint8_t *rflag;        /* [nops] HSC_RD_* | HSC_LRD_*; with HSC_RESOLVE_ARRAYS */
+    const uint64_t *spine_op;    /* [keys] the read op that is the key's spine; with HSC_RESOLVE_ARRAYS */
+    float ms;                    /* device time of the whole call */
+} hsc_lresolved;
+int hsc_dep_graph_resolve_lists(hsc_ctx *ctx, const hsc_lhistory *h, unsigned flags, hsc_lresolved *out);
+/* A build of the last list resolve's ncommitted txns (cid space) from its edge
+ * rows alone: no ops, the rows take the staged rw pairs' place.  A staged
+ * real-time order (of ncommitted txns) joins as in any build; staged rw pairs
+ * are refused with HSC_EINVAL and stay staged for a later build.
+ * HSC_ESTATE when no list resolve came first.  The anomaly, snapshot-isolation
+ * and SCC entries run unchanged on this build.  Here ww edges may go down in
+ * id, so a cycle of ww edges alone (G0) is possible; hsc_dep_graph_anomalies
+ * classes it G1c, since it is an E1 cycle (see the note there). */
+int hsc_dep_graph_build_lists(hsc_ctx *ctx, int flags, hsc_graph_stats *stats);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst

@@ -714,6 +714,8 @@ struct hsc_ctx {
     ResolveOut resolve_out;
     ListBufs lists;          // hsc_dep_graph_resolve_lists: device scratch and the edge rows, host results
     ListOut lists_out;
+    InternalBufs internal;   // hsc_dep_graph_internal / _internal_lists: device scratch, host results
+    InternalOut internal_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

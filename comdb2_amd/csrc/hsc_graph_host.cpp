@@ -371,6 +371,75 @@ int hsc_dep_graph_build_lists(hsc_ctx *c, int flags, hsc_graph_stats *st)
     return build_stats(c, rc, build_ms, st);
 }
 
+// The internal-consistency pass over the history `in` names (the last
+// successful resolve's, still on the device), timed; r: that resolve's sort
+// rows.  Caller holds c->mu.
+static int internal_timed(hsc_ctx *c, const InternalIn &in, ResolveBufs &r, unsigned flags, hsc_internal_report *out)
+{
+    hipStream_t s = c->stream;
+    const bool arrays = (flags & HSC_INTERNAL_ARRAYS) != 0;
+    EventSpan t;
+    InternalOut &o = c->internal_out;
+    hipError_t e = t.begin(s);
+    if (e == hipSuccess) e = graph_internal(in, r, c->internal, arrays, o, s);
+    if (e == hipSuccess) e = t.end(s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    memset(out, 0, sizeof *out);
+    HIPCHK(c, e);
+    out->nops = o.nops;
+    out->ntxn = o.ntxn;
+    out->checked_reads = o.checked_reads;
+    out->bad_reads = o.bad_reads;
+    out->compared_elements = o.compared_elements;
+    out->bad_txns = o.bad_txns;
+    out->txn_bad = data_or_zero(o.txn_bad);
+    out->n_listed = o.n_listed;
+    out->listed_op = data_or_zero(o.listed_op);
+    out->listed_anchor = data_or_zero(o.listed_anchor);
+    out->bad = data_or_zero(o.bad);
+    out->anchor_op = data_or_zero(o.anchor_op);
+    out->sort_packed = o.sort_packed;
+    out->ms = o.nops ? t.ms() : 0;
+    return HSC_OK;
+}
+
+int hsc_dep_graph_internal(hsc_ctx *c, unsigned flags, hsc_internal_report *out)
+{
+    if (!c || !out) return HSC_EINVAL;
+    GRAPH_ENTRY(c);
+    ResolveBufs &r = c->resolve;
+    if (!r.valid) return ctx_fail(c, HSC_ESTATE, "no resolved history (hsc_dep_graph_resolve)");
+    InternalIn in{};
+    in.nops = r.in_nops;
+    in.ntxn = r.in_ntxn;
+    in.txn = r.in_txn.as<uint32_t>();
+    in.key = r.in_key.as<uint64_t>();
+    in.isw = r.in_isw.as<uint8_t>();
+    in.value = r.in_val.as<uint64_t>();
+    in.level = r.level.as<uint32_t>();
+    return internal_timed(c, in, r, flags, out);
+}
+
+int hsc_dep_graph_internal_lists(hsc_ctx *c, unsigned flags, hsc_internal_report *out)
+{
+    if (!c || !out) return HSC_EINVAL;
+    GRAPH_ENTRY(c);
+    ListBufs &l = c->lists;
+    if (!l.valid) return ctx_fail(c, HSC_ESTATE, "no resolved list history (hsc_dep_graph_resolve_lists)");
+    InternalIn in{};
+    in.nops = l.in_nops;
+    in.ntxn = l.in_ntxn;
+    in.txn = l.in_txn.as<uint32_t>();
+    in.key = l.in_key.as<uint64_t>();
+    in.isw = l.in_isw.as<uint8_t>();
+    in.value = l.in_val.as<uint64_t>();
+    in.off = l.in_off.as<uint64_t>();
+    in.elems = l.in_elems.as<uint64_t>();
+    in.status = l.in_status.as<uint8_t>();
+    in.lists = true;
+    return internal_timed(c, in, l.t, flags, out);
+}
+
 int hsc_dep_graph_stage_rw_pairs(hsc_ctx *c, uint32_t nrs, const uint32_t *readset_txn,
                                  size_t ncommit, const uint64_t *commit_lsn,
                                  const uint32_t *commit_txn)

@@ -733,6 +733,8 @@ struct ResolveBufs {
     size_t kept = 0;       // lowered ops
     uint32_t nc = 0;       // their txns
     bool valid = false;    // a resolve succeeded and its lowered ops are in place
+    size_t in_nops = 0;    // the history in_* holds since then (graph_internal reads it)
+    uint32_t in_ntxn = 0;
     int sort_path = 0;     // bit 0: the lookup table's sort ran packed, bit 1: the finality sort did
     void release_all();
 };
@@ -799,6 +801,8 @@ struct ListBufs {
     size_t n_rows = 0;     // edge rows (holes included)
     uint32_t nc = 0;       // committed txns
     bool valid = false;    // a list resolve succeeded and its rows are in place
+    size_t in_nops = 0;    // the history in_* holds since then (graph_internal reads it)
+    uint32_t in_ntxn = 0;
     void release_all();
 };
 struct ListIn {  // host pointers
@@ -821,6 +825,42 @@ struct ListOut {  // host results (hsc_lresolved points into them)
 };
 hipError_t graph_resolve_lists(const ListIn &in, ListBufs &l, bool arrays, ListOut &out, hipStream_t s);
 hipError_t warm_lists();
+// Internal consistency (hsc_intcons.hip): every read against its
+// txn's own earlier ops on the key, over the history a resolve left on the
+// device (in.* are device pointers into ResolveBufs::in_* / ListBufs::in_*).
+// The (txn, key) sort goes through r's sort rows and scratch (sort_rows2); the
+// rest lives in buffers of its own, so what the resolve left for the build --
+// the lowered ops, the edge rows, cid, level, txn_of_cid -- stays as it is.
+struct InternalBufs {
+    DBuf rows, pay;                 // the (txn, key) rows and their ops
+    DBuf bad, anchor;               // per op
+    DBuf f0, f1, bpos;              // flags / scans, the boundaries' positions
+    DBuf plane, ct, list_op, list_anchor;
+    void release_all();
+};
+struct InternalIn {  // device pointers
+    size_t nops;
+    uint32_t ntxn;
+    const uint32_t *txn;
+    const uint64_t *key;
+    const uint8_t *isw;
+    const uint64_t *value;
+    const uint64_t *off, *elems;  // list histories
+    const uint8_t *status;        // list histories: only OK txns are checked
+    const uint32_t *level;        // value histories: != 0 inside C (the counters' txns)
+    bool lists;
+};
+struct InternalOut {  // host results (hsc_internal_report points into them)
+    std::vector<uint8_t> txn_bad, bad;
+    std::vector<uint64_t> listed_op, listed_anchor, anchor_op;
+    size_t nops;
+    uint32_t ntxn, bad_txns, n_listed;
+    uint64_t checked_reads, bad_reads, compared_elements;
+    int sort_packed;
+};
+hipError_t graph_internal(const InternalIn &in, ResolveBufs &r, InternalBufs &b, bool arrays, InternalOut &out,
+                          hipStream_t s);
+hipError_t warm_internal();
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {

@@ -686,6 +686,8 @@ hipError_t graph_resolve_lists(const ListIn &in, ListBufs &l, bool arrays, ListO
     CK(hipStreamSynchronize(s));
     l.n_rows = n_rows;
     l.nc = nc;
+    l.in_nops = n;
+    l.in_ntxn = nt;
     l.valid = true;
     return hipSuccess;
 }

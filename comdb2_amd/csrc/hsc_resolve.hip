@@ -607,6 +607,8 @@ hipError_t graph_resolve(const ResolveIn &in, ResolveBufs &r, bool arrays, int d
     CK(hipStreamSynchronize(s));
     r.kept = kept;
     r.nc = nc;
+    r.in_nops = n;
+    r.in_ntxn = nt;
     r.valid = true;
     return hipSuccess;
 }

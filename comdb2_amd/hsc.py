@@ -191,6 +191,22 @@ LRESOLVED_COUNTERS = ("nops", "ntxn", "ncommitted", "recovered", "aborted", "dro
                       "internal_reads", "unobserved_appends", "g1a_txns", "g1b_txns", "n_listed")
 
 
+INTERNAL_ARRAYS = 1
+INTERNAL_LIST_CAP = 4096
+
+
+class InternalReport(C.Structure):
+    """hsc_internal_report: the arrays are host memory of the context."""
+    _fields_ = [("nops", C.c_size_t), ("ntxn", C.c_uint32), ("checked_reads", C.c_uint64),
+                ("bad_reads", C.c_uint64), ("compared_elements", C.c_uint64), ("bad_txns", C.c_uint32),
+                ("txn_bad", _p), ("n_listed", C.c_uint32), ("listed_op", _p), ("listed_anchor", _p),
+                ("bad", _p), ("anchor_op", _p), ("sort_packed", C.c_int), ("ms", C.c_float)]
+
+
+INTERNAL_COUNTERS = ("nops", "ntxn", "checked_reads", "bad_reads", "compared_elements", "bad_txns", "n_listed",
+                     "sort_packed")
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -266,6 +282,7 @@ EXPORTS = [
     "hsc_dep_graph_anomalies", "hsc_dep_graph_si",
     "hsc_dep_graph_resolve", "hsc_dep_graph_build_resolved", "hsc_dep_graph_resolve_sort_path",
     "hsc_dep_graph_resolve_lists", "hsc_dep_graph_build_lists",
+    "hsc_dep_graph_internal", "hsc_dep_graph_internal_lists",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -360,6 +377,8 @@ def load() -> C.CDLL:
         "hsc_dep_graph_resolve_sort_path": (C.c_int, [_p]),
         "hsc_dep_graph_resolve_lists": (C.c_int, [_p, C.POINTER(_LHistory), C.c_uint, C.POINTER(LResolved)]),
         "hsc_dep_graph_build_lists": (C.c_int, [_p, C.c_int, C.POINTER(GraphStats)]),
+        "hsc_dep_graph_internal": (C.c_int, [_p, C.c_uint, C.POINTER(InternalReport)]),
+        "hsc_dep_graph_internal_lists": (C.c_int, [_p, C.c_uint, C.POINTER(InternalReport)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
         "hsc_window_ingest_raw": (C.c_int, [_p, C.POINTER(_RawLog)]),
@@ -1314,6 +1333,36 @@ class Validator:
         self._chk(self.lib.hsc_dep_graph_build_lists(self.ctx, 1 if full else 0, C.byref(st)),
                   "hsc_dep_graph_build_lists")
         return st.as_dict()
+
+    def _internal(self, fn, name: str, arrays: bool) -> dict:
+        a = InternalReport()
+        self._chk(fn(self.ctx, INTERNAL_ARRAYS if arrays else 0, C.byref(a)), name)
+        arr = _copy_out
+        out = {k: getattr(a, k) for k in INTERNAL_COUNTERS + ("ms",)}
+        out["txn_bad"] = arr(a.txn_bad, a.ntxn, np.uint8)
+        out["listed_op"] = arr(a.listed_op, a.n_listed, np.uint64)
+        out["listed_anchor"] = arr(a.listed_anchor, a.n_listed, np.uint64)
+        out["bad"] = arr(a.bad, a.nops, np.uint8) if arrays else None
+        out["anchor_op"] = arr(a.anchor_op, a.nops, np.uint64) if arrays else None
+        return out
+
+    def graph_internal(self, arrays: bool = False) -> dict:
+        """Internal consistency of the value history the last dep_graph_resolve
+        uploaded (hsc_dep_graph_internal): every read against its txn's
+        previous op on the key.  Nothing is uploaded and nothing the resolve
+        left for dep_graph_build_resolved is touched; callable any number of
+        times until the next resolve.  Copies of every field; without
+        ``arrays`` the per-op bad / anchor_op are None.  (Named outside the
+        ``dep_graph_`` prefix like the list entries, for the same inventory;
+        tests/test_gpu_internal.py covers this and graph_internal_lists.)"""
+        return self._internal(self.lib.hsc_dep_graph_internal, "hsc_dep_graph_internal", arrays)
+
+    def graph_internal_lists(self, arrays: bool = False) -> dict:
+        """Internal consistency of the list-append history the last
+        graph_resolve_lists uploaded (hsc_dep_graph_internal_lists): every
+        read of an OK txn against its txn's previous read of the key and the
+        txn's own appends since.  As graph_internal otherwise."""
+        return self._internal(self.lib.hsc_dep_graph_internal_lists, "hsc_dep_graph_internal_lists", arrays)
 
     def probe_device(self, batch: ProbeBatch) -> None:
         self._chk(self.lib.hsc_probe_device(self.ctx, C.byref(batch)), "hsc_probe_device")

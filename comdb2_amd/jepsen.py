@@ -62,7 +62,11 @@ committed, and run the analyses of ``check_edn`` on the committed part.
 :func:`check_dirty_reads_edn` does the resolve alone for the reference's
 dirty-reads workload (linearizable/jepsen/src/comdb2/core.clj:320-353,
 :492-523: "a failed transaction whose value became visible to some read").
-Internal consistency (a txn reading its own earlier write) is not checked.
+Internal consistency (a txn reading its own earlier ops, Elle's ``:internal``)
+is checked on request: ``check_txn_edn(..., internal=True)`` and
+``check_append_edn(..., internal=True)`` run ``Validator.graph_internal`` /
+``graph_internal_lists`` on the history the resolve uploaded
+(:func:`internal_reads`, :func:`internal_list_reads`, :func:`with_internal`).
 
 Both conversions above take completion order for commit order, which a Jepsen
 history does not carry.  A list-append history needs no such premise:
@@ -612,8 +616,89 @@ def listed_reads(vh: ValueHistory, res: dict) -> dict:
     return out
 
 
+# ---------------------------------------------------------------------------
+# internal consistency (Elle's :internal): a txn's reads against its own ops
+# ---------------------------------------------------------------------------
+_INTERNAL_STATS = ("nops", "ntxn", "checked_reads", "bad_reads", "compared_elements", "bad_txns", "n_listed",
+                   "sort_packed", "ms")
+_INTERNAL_LEVELS = ("snapshot_isolation", "serializable", "strict_serializable", "strong_snapshot_isolation")
+
+
+def _internal_keys(entries: list, res: dict) -> dict:
+    return {"internal_anomalies": entries, "internal_anomaly_count": int(res["bad_reads"]),
+            "internal": {k: res[k] for k in _INTERNAL_STATS if k in res}}
+
+
+def internal_reads(vh: ValueHistory, res: dict) -> dict:
+    """``internal_anomalies`` of a ``Validator.graph_internal`` dict (a pure
+    function of its arguments): one entry {txn, key, op, anchor_op, expected,
+    got} per listed bad read -- ``anchor_op`` the txn's previous op on the key
+    and ``expected`` its value, ``got`` what the read returned (None for the
+    initial state either way); the exact ``internal_anomaly_count`` (the list
+    stops at the entry's cap) and ``internal``, the entry's scalar stats."""
+    def val(i):
+        v = int(vh.value[i])
+        return None if v == VAL_INIT else v
+
+    entries = [{"txn": int(vh.txn[i]), "key": int(vh.key[i]), "op": int(i), "anchor_op": int(a),
+                "expected": val(int(a)), "got": val(int(i))}
+               for i, a in zip(res["listed_op"], res["listed_anchor"])]
+    return _internal_keys(entries, res)
+
+
+def internal_list_reads(lh: ListHistory, res: dict) -> dict:
+    """:func:`internal_reads` for a ``Validator.graph_internal_lists`` dict: one
+    entry {txn, key, op, anchor_op, prefix, appended, got} per listed bad
+    read -- ``prefix`` the list of the txn's previous read of the key
+    (``anchor_op``), or None when there is none and ``anchor_op`` is the txn's
+    first append to the key; ``appended`` the elements the txn appended to the
+    key since; ``got`` the list the read returned, which should have been
+    prefix + appended, or have ended in appended."""
+    txn, key, isw = np.asarray(lh.txn), np.asarray(lh.key), np.asarray(lh.is_write)
+
+    def lst(i):
+        return [int(x) for x in lh.elems[int(lh.list_off[i]):int(lh.list_off[i + 1])]]
+
+    entries = []
+    for i, a in zip(res["listed_op"], res["listed_anchor"]):
+        i, a = int(i), int(a)
+        has_p = not isw[a]
+        lo = a + 1 if has_p else a
+        mine = np.nonzero((txn[lo:i] == txn[i]) & (key[lo:i] == key[i]) & (isw[lo:i] != 0))[0] + lo
+        entries.append({"txn": int(txn[i]), "key": int(key[i]), "op": i, "anchor_op": a,
+                        "prefix": lst(a) if has_p else None, "appended": [int(lh.value[j]) for j in mine],
+                        "got": lst(i)})
+    return _internal_keys(entries, res)
+
+
+def with_internal(report: dict, keys: dict) -> dict:
+    """A check_txn_edn / check_append_edn report with the keys of
+    :func:`internal_reads` / :func:`internal_list_reads` merged in (a pure
+    function: a new dict, ``levels`` copied): ``anomaly_types`` gains
+    "internal" and ``valid`` turns False when there is a bad read; ``levels``,
+    when the report has them, gains ``internal_consistent``, and every level
+    present among snapshot_isolation, serializable, strict_serializable and
+    strong_snapshot_isolation is and-ed with it -- the INT axiom is part of
+    read atomic, which all four imply.  ``read_committed`` and ``g1c_free`` stay
+    as they are: PL-2 says nothing about a txn's own writes."""
+    out = dict(report)
+    out.update(keys)
+    ok = int(keys["internal_anomaly_count"]) == 0
+    if not ok:
+        out["anomaly_types"] = sorted(set(report["anomaly_types"]) | {"internal"})
+        out["valid"] = False
+    if "levels" in report:
+        levels = dict(report["levels"])
+        levels["internal_consistent"] = ok
+        for name in _INTERNAL_LEVELS:
+            if name in levels:
+                levels[name] = bool(levels[name]) and ok
+        out["levels"] = levels
+    return out
+
+
 def check_txn_edn(validator, text: str, witness: bool = True, realtime: bool = False,
-                  isolation: bool = False) -> dict:
+                  isolation: bool = False, internal: bool = False) -> dict:
     """A multi-op txn history through the GPU by value: resolve every read to
     the write it observed (``Validator.dep_graph_resolve``), build the graph
     of the committed part (``dep_graph_build_resolved``) and run exactly the
@@ -626,10 +711,19 @@ def check_txn_edn(validator, text: str, witness: bool = True, realtime: bool = F
     ``isolation``) gains ``read_committed`` = no G1a, no G1b and
     ``g1c_free``; ``resolve`` holds the entry's stats, ``history`` the
     :class:`TxnOps`.  With ``realtime`` the intervals of the committed txns
-    are staged; a recovered txn is open.  Internal consistency is not
-    checked."""
+    are staged; a recovered txn is open.
+
+    ``internal``: also internal consistency (``Validator.graph_internal``, run
+    right after the resolve on the history it uploaded): the report becomes
+    :func:`with_internal`'s -- ``internal_anomalies``,
+    ``internal_anomaly_count``, ``internal``, "internal" among
+    ``anomaly_types``, ``valid`` False on any bad read, and with ``isolation``
+    ``levels["internal_consistent"]`` and-ed into the levels from snapshot
+    isolation up.  Without it internal consistency is not checked and the
+    report is as it always was."""
     tx = vhistory_from_txn_edn(text)
     res = validator.dep_graph_resolve(tx.vhistory, arrays=True)
+    own = internal_reads(tx.vhistory, validator.graph_internal()) if internal else None
     toc = [int(t) for t in res["txn_of_cid"]]
     sel = np.asarray(toc, np.int64)
     committed = TxnOps(tx.vhistory, tx.ok, tx.failed, tx.info, tx.unpaired, [tx.txn_ops[t] for t in toc],
@@ -650,7 +744,7 @@ def check_txn_edn(validator, text: str, witness: bool = True, realtime: bool = F
         report["levels"]["read_committed"] = not g1a and not g1b and bool(report["levels"]["g1c_free"])
     report["resolve"] = {k: res[k] for k in _RESOLVE_STATS if k in res}
     report["resolve_arrays"] = {k: res[k] for k in ("fate", "cid", "txn_of_cid", "txn_g1")}
-    return report
+    return report if own is None else with_internal(report, own)
 
 
 # ---------------------------------------------------------------------------
@@ -736,7 +830,7 @@ def listed_list_reads(lh: ListHistory, res: dict) -> dict:
 
 
 def check_append_edn(validator, text: str, witness: bool = True, realtime: bool = False,
-                     isolation: bool = False) -> dict:
+                     isolation: bool = False, internal: bool = False) -> dict:
     """A list-append history through the GPU with no premise on commit order:
     the version order of every key is its longest read
     (``Validator.graph_resolve_lists``), the graph is built from the edges
@@ -760,9 +854,15 @@ def check_append_edn(validator, text: str, witness: bool = True, realtime: bool 
     (with ``isolation``) gains ``read_committed``.  ``resolve`` holds the
     entry's stats, ``history`` the :class:`AppendOps`.  A dangling read is
     listed and counted, and does not by itself make the history invalid, as
-    in :func:`check_txn_edn`.  Internal consistency is not checked."""
+    in :func:`check_txn_edn`.
+
+    ``internal``: also internal consistency (``Validator.graph_internal_lists``,
+    run right after the resolve), reported as :func:`check_txn_edn` does with
+    :func:`internal_list_reads`' entries.  Without it internal consistency is
+    not checked and the report is as it always was."""
     tx = lhistory_from_append_edn(text)
     res = validator.graph_resolve_lists(tx.lhistory, arrays=True)
+    own = internal_list_reads(tx.lhistory, validator.graph_internal_lists()) if internal else None
     toc = [int(t) for t in res["txn_of_cid"]]
     sel = np.asarray(toc, np.int64)
     committed = AppendOps(tx.lhistory, tx.ok, tx.failed, tx.info, tx.unpaired, [tx.txn_ops[t] for t in toc],
@@ -791,7 +891,7 @@ def check_append_edn(validator, text: str, witness: bool = True, realtime: bool 
         report["levels"]["read_committed"] = not g1 and bool(report["levels"]["g1c_free"])
     report["resolve"] = {k: res[k] for k in _LRESOLVE_STATS if k in res}
     report["resolve_arrays"] = {k: res[k] for k in ("fate", "cid", "txn_of_cid", "txn_g1")}
-    return report
+    return report if own is None else with_internal(report, own)
 
 
 # ---- the reference's dirty-reads workload (core.clj:320-353, :492-523) ------

@@ -913,7 +913,8 @@ int hsc_dep_graph_anomalies(hsc_ctx *ctx, unsigned flags, unsigned max_anti_batc
  * Scope: this is the dependency-graph condition only.  The graph is built
  * from committed txns: aborted and intermediate reads (G1a, G1b) are reported
  * by hsc_dep_graph_resolve (below) for a history given with its values, not by
- * this call; internal consistency is not checked anywhere.  With a staged real-time order the definitions hold unchanged
+ * this call; internal consistency by hsc_dep_graph_internal / _internal_lists
+ * (below).  With a staged real-time order the definitions hold unchanged
  * over the widened E1, and the verdict is strong snapshot isolation.
  * HSC_SI_WITNESS: per flagged component one simple cycle of >= 2 of its txns,
  * wit_txn[wit_off[i], wit_off[i + 1]), every step an edge of the build with
@@ -972,7 +973,9 @@ int hsc_dep_graph_si(hsc_ctx *ctx, unsigned flags, hsc_si_report *out);
  * G1b: a read with HSC_RD_INTERMEDIATE; txn_g1[r] bit 1 / bit 2: r is in C and
  * has such a read.
  * Internal consistency (a txn that reads k after writing k must see its own
- * last write) is NOT checked: an internal read is only counted.
+ * last write) is not checked by this entry, which only counts an internal
+ * read: hsc_dep_graph_internal (below) checks it on the history this entry
+ * uploaded.
  * Lowering: cid[t] = the dense rank of t among C in ascending id, 0xFFFFFFFF
  * outside C; txn_of_cid its inverse.  The kept ops, in array order, are all
  * ops of txns in C except reads flagged DANGLING or ABORTED; a kept op has
@@ -1134,6 +1137,64 @@ int hsc_dep_graph_resolve_lists(hsc_ctx *ctx, const hsc_lhistory *h, unsigned fl
  * id, so a cycle of ww edges alone (G0) is possible; hsc_dep_graph_anomalies
  * classes it G1c, since it is an E1 cycle (see the note there). */
 int hsc_dep_graph_build_lists(hsc_ctx *ctx, int flags, hsc_graph_stats *stats);
+/* ---- internal consistency: a txn's reads against its own earlier ops -------
+ * Elle's :internal, the INT axiom of read atomic: it needs no version order and
+ * no graph, only each txn's own ops.  Both entries are pure functions of the
+ * history the last successful resolve of their kind uploaded
+ * (hsc_dep_graph_internal: hsc_dep_graph_resolve; hsc_dep_graph_internal_lists:
+ * hsc_dep_graph_resolve_lists): they read the device copy, upload nothing, and
+ * leave what the resolve keeps for its build untouched.  Either may be called
+ * any number of times until the next resolve of its kind, before or after the
+ * build, the anomaly / SI entries and staged real-time edges, and answers the
+ * same.  HSC_RD_INTERNAL and internal_reads of the resolves keep their meaning
+ * (a read that observed its own txn's write, counted only).
+ * For a txn t and a key k let o_1 .. o_m be t's ops on k in program order
+ * (array order; they need not be contiguous).
+ * Value histories.  A read o_j with j > 1 is constrained, its anchor o_{j-1}
+ * (a read or a write); it is bad iff value[o_j] != value[o_{j-1}]
+ * (HSC_VAL_INIT compares like any value).  A read with j = 1 is unconstrained.
+ * bad / anchor_op are computed for every read whatever its txn's status; the
+ * counters, txn_bad and the listed reads cover the reads of txns in the
+ * resolve's committed set C, as the resolve's own counters do.
+ * List histories.  Only HSC_TXN_OK txns are checked (the list resolve ignores
+ * every other read throughout; such reads get bad = 0 and no anchor).  For a
+ * read o_j let p be the latest earlier read among o_1 .. o_{j-1}, A the
+ * elements appended by the ops strictly between p and o_j in order (from o_1
+ * when there is no p), a = |A|:
+ *   p exists:          constrained, anchor p; consistent iff len_j == len_p + a
+ *                      and list_j == list_p || A element for element;
+ *   no p, a > 0:       constrained, anchor o_1; consistent iff len_j >= a and
+ *                      the last a elements of list_j equal A;
+ *   no p, a == 0:      unconstrained.
+ * A read is bad iff it is constrained and not consistent.  compared_elements =
+ * the sum over constrained reads whose length condition holds of len_p + a
+ * (p exists) or a (no p): a read that fails the length condition is bad
+ * without an element compared, so the number is exact.
+ * HSC_ESTATE: no successful resolve of the kind came before (also after one
+ * that failed).  HSC_EDEVICE: a host-only context.  HSC_EINVAL: a NULL
+ * argument.  An empty history succeeds with every field zero.  The arrays are
+ * host memory owned by the context, never NULL (bad and anchor_op hold nothing
+ * without HSC_INTERNAL_ARRAYS), valid until the next graph call.  The sharded
+ * path (hsc_multi_graph_scc) has no such entry. */
+#define HSC_INTERNAL_ARRAYS   1      /* flags: also copy the per-op arrays back */
+#define HSC_INTERNAL_LIST_CAP 4096
+typedef struct hsc_internal_report {
+    size_t nops;  uint32_t ntxn;
+    uint64_t checked_reads;        /* counted reads that are constrained */
+    uint64_t bad_reads;            /* of those, the inconsistent ones */
+    uint64_t compared_elements;    /* list histories (above); value histories: 0 */
+    uint32_t bad_txns;
+    const uint8_t  *txn_bad;       /* [ntxn] 1: a counted txn with a bad read */
+    uint32_t n_listed;             /* min(cap, bad_reads) */
+    const uint64_t *listed_op;     /* ascending read op index */
+    const uint64_t *listed_anchor; /* its anchor op */
+    const uint8_t  *bad;           /* [nops]; with HSC_INTERNAL_ARRAYS */
+    const uint64_t *anchor_op;     /* [nops] UINT64_MAX: unconstrained or a write; with HSC_INTERNAL_ARRAYS */
+    int sort_packed;               /* the (txn, key) sort ran as packed single words */
+    float ms;                      /* device time of the whole call */
+} hsc_internal_report;
+int hsc_dep_graph_internal(hsc_ctx *ctx, unsigned flags, hsc_internal_report *out);
+int hsc_dep_graph_internal_lists(hsc_ctx *ctx, unsigned flags, hsc_internal_report *out);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst

@@ -612,7 +612,8 @@ struct hsc_ctx {
     DBuf d_trad16, d_trad16b;  // packed u16 copies of d_trad / d_trad2 (NarrowTiles::trad16)
     int trad_shift = 0;        // d_trad[trad_m + 1]: the table's shift (| kTradLog)
     DBuf d_commits, d_cdir, d_tdir, d_trad, d_done, w_vflags, d_key32, d_rank32, d_ctmp[4];
-    DBuf d_recent;     // the tiles' recent lists (narrow_recent_build), built with d_key32 / d_rank32
+    DBuf d_recent;     // the tiles' recent lists and slot tables (narrow_recent_build), built with d_key32 / d_rank32
+    int slot_qshift = 0;  // the slot tables' quantum (NarrowTiles::qshift), set with them
     DBuf d_fulljoins;  // u32: join blocks / items that staged a whole tile (hsc_batch_stats); every lane adds to it
     Dir16 cdir{}, tdir{};
     uint32_t trad_m = 0;       // tile bucket table size (0: none)

@@ -1018,9 +1018,14 @@ static int device_build(hsc_ctx *c, size_t n_in)
                                          c->cdir, c->rank_lsn32, c->rank_base,
                                          c->d_key32.as<uint32_t>(), c->d_rank32.as<uint32_t>(),
                                          tiles_fused ? nullptr : tiles_flag, s));
+            // the recent lists and the slot tables, rebuilt with every window
+            // (ingest, folds, members): neither can be older than its rows.
+            // The slot maxima's quantum from the window's largest rank32.
+            c->slot_qshift = narrow_slot_qshift(c->rank_lsn32 ? span[1] - span[0] + 1 : c->ncommit);
             HIPCHK(c, c->d_recent.ensure(4 * narrow_recent_words(wn.ntiles)));
             HIPCHK(c, narrow_recent_build(c->d_key32.as<uint32_t>(), c->d_rank32.as<uint32_t>(),
-                                          (uint32_t)c->n, wn.ntiles, c->d_recent.as<uint32_t>(), s));
+                                          (uint32_t)c->n, wn.ntiles, wn.sp_w, c->slot_qshift,
+                                          c->d_recent.as<uint32_t>(), s));
             HIPCHK(c, hipMemcpyAsync(&wide32, tiles_flag, 4, hipMemcpyDeviceToHost, s));  // read below
             tiles32 = true;
         }
@@ -1441,6 +1446,7 @@ static void swap_window(hsc_ctx *a, hsc_ctx *b)
     swap(a->trad_log, b->trad_log), swap(a->ncommit, b->ncommit), swap(a->has_commits, b->has_commits);
     swap(a->commit_span[0], b->commit_span[0]), swap(a->commit_span[1], b->commit_span[1]);
     swap(a->rank_lsn32, b->rank_lsn32), swap(a->rank_base, b->rank_base);
+    swap(a->slot_qshift, b->slot_qshift);  // (travels with d_recent's slot tables)
     swap(a->d_gid, b->d_gid), swap(a->d_words, b->d_words), swap(a->d_lsn, b->d_lsn);
     swap(a->d_gid2, b->d_gid2), swap(a->d_words2, b->d_words2), swap(a->d_lsn2, b->d_lsn2);
     swap(a->d_flags, b->d_flags), swap(a->d_scratch, b->d_scratch);
@@ -2558,10 +2564,11 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
     // chunk-sorted records: each chunk's records in an area of its own, tile
     // runs found by the join through the plan's scan (no scatter pass)
     HIPCHK(c, c->w_tcode2.ensure(2 * (size_t)hist_stride(work.G) * nt));  // cst
-    HIPCHK(c, c->w_tcode.ensure(4 * (size_t)work.G * ((nt + 3) & ~3u)));  // chunk-major rows
+    // chunk-major rows of {kept records' run and count, located records}
+    const size_t cm_words = (size_t)work.G * ((nt + 3) & ~3u);
+    HIPCHK(c, c->w_tcode.ensure(8 * cm_words));
     HIPCHK(c, c->w_trecs.ensure(16 * 2 * (size_t)work.chunk * work.G));
     work.cst = c->w_tcode2.as<uint16_t>();
-    work.cm = c->w_tcode.as<uint32_t>();
     work.hist = c->w_hist.as<uint32_t>();
     work.counts = c->w_counts.as<uint32_t>();
     work.bucket_off = c->w_bucket.as<uint32_t>();
@@ -2591,7 +2598,7 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
     ntl.trad16 = c->trad_m ? c->d_trad16.as<uint16_t>() : nullptr;
     ntl.trad_shift = c->trad_shift;
     ntl.recs = c->w_trecs.as<uint4>();
-    narrow_recent_view(ntl, c->d_recent.as<uint32_t>(), wn.ntiles);
+    narrow_recent_view(ntl, c->d_recent.as<uint32_t>(), wn.ntiles, c->slot_qshift);
     if (!c->d_fulljoins.p) {
         HIPCHK(c, c->d_fulljoins.ensure(4));
         HIPCHK(c, hipMemset(c->d_fulljoins.p, 0, 4));
@@ -2634,6 +2641,12 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
         for (int i = 0; i < 6; ++i)
             if (!c->ev[i]) HIPCHK(c, hipEventCreate(&c->ev[i]));
     if (tm) HIPCHK(c, hipEventRecord(c->ev[0], s));
+    // the table's layout goes with the locate instance: two-word entries
+    // where its filter makes located != kept, one word otherwise
+    if (narrow_locate_fast(c->nv, ntl, p))
+        work.cmx = c->w_tcode.as<uint2>();
+    else
+        work.cm = c->w_tcode.as<uint32_t>();
     int shape = -1;
     HIPCHK(c, launch_locate_t(c->nv, wn, p, work, ntl, flags, s, &shape));
     if (shape >= 0) (shape ? c->nt_fast : c->nt_general)++;

@@ -240,6 +240,12 @@ struct ProbeWork {
     // t's run starts in it; join items are tile-local record ranges
     uint16_t *cst;
     uint32_t *cm;  // [G][round4(ntiles)] chunk-major (run start << 16 | count), the locate's rows
+    // narrow tiles: the same table with a second word per entry, {run start
+    // << 16 | count of the records the locate kept, records its end-tile step
+    // located before its slot filter dropped any}, same row stride (in
+    // entries); the hot-tile rule reads the second word.  cm is null then.
+    // (null: compact tiles, where every located record is kept)
+    uint2 *cmx;
     // the batch's verdict bitmap, built in place of a pack pass (narrow and
     // compact tiles): k_plan_s writes the locate's flags as whole words, the
     // join ORs its hits in (null: verdict bytes only)
@@ -250,7 +256,7 @@ struct ProbeWork {
     // k_plan_s writes them)
     uint8_t *vout;
     uint32_t n_txn;
-    // hot-tile feedback: a tile of more than kTileCap records stores `batch`
+    // hot-tile feedback: a tile of more than kTileCap located records stores `batch`
     // (the context's count of narrow-tile batches, from 1) into this word of
     // mapped host memory, which the host reads when it picks the next batches'
     // path (null: none)
@@ -388,18 +394,42 @@ struct NarrowTiles {
     // of a row left out: a record with r(S) >= rtheta[t] needs the list only
     const uint32_t *rkey32, *rrank32;  // [ntiles][256]
     const uint32_t *rtheta;            // [ntiles]
+    // slot table (k_recent): per tile kSlots equal key slots, slot of a row =
+    // key32 >> shift (narrow_slot_shift of the tile's span); each holds the
+    // largest rank32 of its rows >> qshift (0: no row).  qshift: the least q
+    // with (the window's largest rank32) >> q < 65536.
+    const uint16_t *slots;             // [ntiles][kSlots]
+    int qshift;
 };
+constexpr uint32_t kSlotsLog2 = 9, kSlots = 1u << kSlotsLog2;
+// span = the next tile's first code - this tile's, clamped to [1, 2^32] (2^32
+// for the last tile): the least s with (span - 1) >> s < kSlots
+__host__ __device__ inline int narrow_slot_shift(uint64_t span)
+{
+    const uint32_t x = span > 0xFFFFFFFFull ? 0xFFFFFFFFu : span ? (uint32_t)(span - 1) : 0;
+    const int bits = x ? 32 - __builtin_clz(x) : 0;
+    return bits > (int)kSlotsLog2 ? bits - (int)kSlotsLog2 : 0;
+}
+// the least q with max_rank >> q < 65536
+inline int narrow_slot_qshift(uint64_t max_rank)
+{
+    int q = 0;
+    while ((max_rank >> q) >= 65536) ++q;
+    return q;
+}
 hipError_t check_sorted_u64(const uint64_t *v, size_t n, uint32_t *flag, hipStream_t s);
 // rank32 by a search of cdir (the 16-ary directory over the commit LSNs C)
 hipError_t narrow_tiles_build(const uint64_t *key64, const uint64_t *lsn, uint32_t n, uint32_t len,
                               const Dir16 &cdir, int rank_lsn32, uint64_t rank_base,
                               uint32_t *key32, uint32_t *rank32, uint32_t *flag, hipStream_t s);
 // The tiles' recent lists from final key32 / rank32 (either rank mode) into
-// `recent`, narrow_recent_words(ntiles) u32s; narrow_recent_view points nt at them.
+// `recent`, narrow_recent_words(ntiles) u32s, with the tiles' slot tables
+// behind them (first: the tiles' first codes; qshift: narrow_slot_qshift of
+// the window's largest rank32); narrow_recent_view points nt at them.
 size_t narrow_recent_words(uint32_t ntiles);
 hipError_t narrow_recent_build(const uint32_t *key32, const uint32_t *rank32, uint32_t n, uint32_t ntiles,
-                               uint32_t *recent, hipStream_t s);
-void narrow_recent_view(NarrowTiles &nt, const uint32_t *recent, uint32_t ntiles);
+                               const uint64_t *first, int qshift, uint32_t *recent, hipStream_t s);
+void narrow_recent_view(NarrowTiles &nt, const uint32_t *recent, uint32_t ntiles, int qshift);
 // r(S) of lsn32 mode: lsn > S <=> lsn - base + 1 > r(S)
 __host__ __device__ inline uint32_t lsn32_rank(uint64_t S, uint64_t base)
 {
@@ -516,7 +546,11 @@ hipError_t launch_plan_s(const ProbeWork &work, uint32_t ntiles, uint32_t *ctl, 
 hipError_t launch_pack_flags(uint8_t *flags, uint32_t n_txn, uint8_t *verdict, uint64_t *bitmap,
                              hipStream_t s);
 // *shape (unless null): the instance launched -- 1 a fast one (built for the
-// window's shape), 0 the general one, -1 none (an empty batch)
+// window's shape), 0 the general one, -1 none (an empty batch).  The caller
+// picks the table's layout by narrow_locate_fast: work.cmx (two-word entries)
+// for a fast instance, work.cm otherwise, the other one null; a mismatch is
+// hipErrorInvalidValue.
+bool narrow_locate_fast(const NarrowView &nv, const NarrowTiles &nt, const ProbeView &p);
 hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeView &p,
                            const ProbeWork &work, const NarrowTiles &nt, uint8_t *verdict,
                            hipStream_t s, int *shape = nullptr);
@@ -524,7 +558,7 @@ hipError_t launch_join_t(const ProbeWork &work, const NarrowTiles &nt, uint32_t 
                          uint32_t ntiles, uint32_t max_items, uint8_t *verdict, hipStream_t s,
                          uint32_t extra_blocks = 512);
 // The join without a plan before it (work.vout set, as for this batch's
-// locate): one block per tile, which scans its tile's column of work.cm, runs
+// locate): one block per tile, which scans its tile's column of work.cmx / work.cm, runs
 // every record of the tile (rounds of kJoinChunk) and moves its share of the
 // locate's flags into the verdict bytes (and bitmap), clearing them.
 hipError_t launch_join_col(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,

@@ -1078,23 +1078,41 @@ __device__ __forceinline__ uint32_t recent_scan(uint32_t x, uint32_t *ws)
     return run;
 }
 
+// The tile's slot table from the same staged rows: smax[key32 >> shift] takes
+// the row's rank by an LDS max, and slot i of the tile is stored as
+// smax[i] >> qshift (NarrowTiles::slots; join records the locate may drop).
+// The tile's span comes from the first codes, as the locate derives it.
+__device__ __forceinline__ uint64_t slot_span(const uint64_t *first, uint32_t tile, uint32_t ntiles)
+{
+    const uint64_t sp = tile + 1 < ntiles ? first[tile + 1] - first[tile] : 1ull << 32;
+    return sp > (1ull << 32) ? 1ull << 32 : sp;
+}
+
 __global__ __launch_bounds__(kRecentThreads) void k_recent(const uint32_t *key32, const uint32_t *rank32,
                                                            uint32_t n, uint32_t *rkey32, uint32_t *rrank32,
-                                                           uint32_t *rtheta)
+                                                           uint32_t *rtheta, const uint64_t *first,
+                                                           int qshift, uint16_t *slots)
 {
     constexpr uint32_t T = 1u << kTLog2;
+    static_assert(kSlots <= kRecentThreads, "a slot per thread");
     __shared__ __attribute__((aligned(16))) uint32_t sk[T];  // the tile's keys as stored (eyt12 order)
     __shared__ uint32_t cnt[32], ws[2][kRecentThreads / 64], lk[kRecent], lr[kRecent], theta;
+    __shared__ uint32_t smax[kSlots];
     const uint32_t tile = blockIdx.x, t = threadIdx.x, lane = t & 63;
     const size_t ts = (size_t)tile << kTLog2;
     const uint32_t tn = min(T, n - (tile << kTLog2));
     const u32x4 rq = *(const u32x4 *)(rank32 + ts + 4 * t);
     ((u32x4 *)sk)[t] = *(const u32x4 *)(key32 + ts + 4 * t);
+    const int shift = narrow_slot_shift(slot_span(first, tile, gridDim.x));
     const uint32_t rv[4] = {rq.x, rq.y, rq.z, rq.w};
     if (t < 32) cnt[t] = 0;
     if (t < kRecent) lk[t] = 0xFFFFFFFFu, lr[t] = 0;
+    if (t < kSlots) smax[t] = 0;
     if (t == 0) theta = 0;
     __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (4 * t + k < tn) atomicMax(&smax[min(sk[eyt12(4 * t + k)] >> shift, kSlots - 1)], rv[k]);
     // v = the R-th largest rank, take = how many of the rows equal to v are
     // members (tn <= R: every row is one -- pads have rank 0, rows >= 1)
     uint32_t v = 0, take = kRecent;
@@ -1147,24 +1165,29 @@ __global__ __launch_bounds__(kRecentThreads) void k_recent(const uint32_t *key32
         rrank32[(size_t)tile * kRecent + t] = lr[t];
     }
     if (t == 0) rtheta[tile] = theta;
+    if (t < kSlots) slots[(size_t)tile * kSlots + t] = (uint16_t)(smax[t] >> qshift);
 }
 
-size_t narrow_recent_words(uint32_t ntiles) { return (size_t)ntiles * (2 * kRecent + 1); }
+// lists, rtheta, then the slot tables (kSlots u16 per tile)
+size_t narrow_recent_words(uint32_t ntiles) { return (size_t)ntiles * (2 * kRecent + 1 + kSlots / 2); }
 
 hipError_t narrow_recent_build(const uint32_t *key32, const uint32_t *rank32, uint32_t n, uint32_t ntiles,
-                               uint32_t *recent, hipStream_t s)
+                               const uint64_t *first, int qshift, uint32_t *recent, hipStream_t s)
 {
     if (ntiles == 0) return hipSuccess;
     uint32_t *rkey = recent, *rrank = rkey + (size_t)ntiles * kRecent, *rtheta = rrank + (size_t)ntiles * kRecent;
-    k_recent<<<ntiles, kRecentThreads, 0, s>>>(key32, rank32, n, rkey, rrank, rtheta);
+    k_recent<<<ntiles, kRecentThreads, 0, s>>>(key32, rank32, n, rkey, rrank, rtheta, first, qshift,
+                                               (uint16_t *)(rtheta + ntiles));
     return hipGetLastError();
 }
 
-void narrow_recent_view(NarrowTiles &nt, const uint32_t *recent, uint32_t ntiles)
+void narrow_recent_view(NarrowTiles &nt, const uint32_t *recent, uint32_t ntiles, int qshift)
 {
     nt.rkey32 = recent;
     nt.rrank32 = recent + (size_t)ntiles * kRecent;
     nt.rtheta = nt.rrank32 + (size_t)ntiles * kRecent;
+    nt.slots = (const uint16_t *)(nt.rtheta + ntiles);
+    nt.qshift = qshift;
 }
 
 // ---- 16-ary directories over sorted u64 arrays ----
@@ -1728,6 +1751,38 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
     LocDefer<K> dfr;
 #pragma unroll
     for (int k = 0; k < K; ++k) dfr.x[k] = 1, dfr.y[k] = 0;
+    // A sub-chunk's candidate records get their in-chunk ranks here (fast
+    // shapes; the general ones take them where the record is formed).  One LDS
+    // word per tile: kept records in the low half (the returning add gives
+    // the rank), located ones in the high half -- at most 4096 of a chunk
+    // reach a tile, so no carry crosses.  A record the slot filter drops (sm:
+    // the two slot maxima of each of the probe's records, ~0 = not tried)
+    // adds to the located half only, without returning, and is gone.
+    uint32_t sm[K][4];  // (not tried = 0xFFFFFFFF: no r(S) >> qshift is above it)
+    auto commit = [&](int s) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            uint4 &a = R0[s][k], &b = R1[s][k];
+            bool drop_a = false, drop_b = false;
+            if constexpr (kFast) {
+                const uint32_t qr = a.w >> nt.qshift;  // (both records carry the probe's r(S))
+                drop_a = max(sm[k][0], sm[k][1]) < qr;
+                drop_b = max(sm[k][2], sm[k][3]) < (b.w >> nt.qshift);
+            }
+            if (a.x != kNoTile32) {
+                if (!drop_a)
+                    a.x |= atomicAdd(&hist[a.x >> 12], 0x10001u) & 0xFFFFu;
+                else
+                    atomicAdd(&hist[a.x >> 12], 0x10000u), a.x = kNoTile32;
+            }
+            if (b.x != kNoTile32) {
+                if (!drop_b)
+                    b.x |= atomicAdd(&hist[b.x >> 12], 0x10001u) & 0xFFFFu;
+                else
+                    atomicAdd(&hist[b.x >> 12], 0x10000u), b.x = kNoTile32;
+            }
+        }
+    };
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const int cb = s & 1;
@@ -1788,6 +1843,10 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
             else
                 dir16_count<2 * K>(nt.tdir, tfirst, keys, act, cnt);
         }
+        // the previous sub-chunk's records: its slot reads have had this
+        // sub-chunk's codes and search to arrive
+        if constexpr (kFast)
+            if (s > 0) commit(s - 1);
         // records of the partly covered end tiles; the fully covered tiles
         // between them (and fully covered end tiles) become one deferred
         // range-maximum check [x, y]
@@ -1796,6 +1855,7 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
             dfr.x[k] = 1, dfr.y[k] = 0;
             R0[s][k].x = R1[s][k].x = kNoTile32;
             RT[s][k] = tx[cb][k];
+            if constexpr (kFast) sm[k][0] = sm[k][1] = sm[k][2] = sm[k][3] = 0xFFFFFFFFu;
             if (!valid[cb][k]) continue;
             const uint32_t q = qq[cb][k];
             const uint32_t ca = cnt[2 * k], cbt = cnt[2 * k + 1];
@@ -1817,11 +1877,31 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
                 if (a == bt && !(use_a && full_a)) dfr.x[k] = 1, dfr.y[k] = 0;
                 dfr.q[k] = q;
                 dfr.snap[k] = snap[cb][k];
-                if (use_a && !full_a)
-                    r0 = make_uint4(a << 12 | atomicAdd(&hist[a], 1u), (uint32_t)lo_a,
-                                    (uint32_t)min(hi_a, 0xFFFFFFFFull), rs[k]);
-                if (use_b && !full_b)
-                    r1 = make_uint4(bt << 12 | atomicAdd(&hist[bt], 1u), 0, (uint32_t)hi_b, rs[k]);
+                const bool rec_a = use_a && !full_a, rec_b = use_b && !full_b;
+                const uint32_t la = (uint32_t)lo_a, ha = (uint32_t)min(hi_a, 0xFFFFFFFFull);
+                const uint32_t hb = (uint32_t)hi_b;
+                if constexpr (kFast) {  // candidates: the in-chunk rank comes with commit()
+                    if (rec_a) r0 = make_uint4(a << 12, la, ha, rs[k]);
+                    if (rec_b) r1 = make_uint4(bt << 12, 0, hb, rs[k]);
+                } else {  // the general shapes drop nothing: the word is a plain count
+                    if (rec_a) r0 = make_uint4(a << 12 | atomicAdd(&hist[a], 1u), la, ha, rs[k]);
+                    if (rec_b) r1 = make_uint4(bt << 12 | atomicAdd(&hist[bt], 1u), 0, hb, rs[k]);
+                }
+                // the slot filter (fast shapes): a record whose bounds reach at
+                // most two adjacent slots of its tile, both with every row
+                // older than the snapshot's quantum, meets no newer row.  Both
+                // records' table reads go out here and are looked at one
+                // sub-chunk later (commit), behind that one's end-tile search.
+                if constexpr (kFast) {
+                    const uint16_t *sa = nt.slots + (size_t)a * kSlots, *sb2 = nt.slots + (size_t)bt * kSlots;
+                    const int sha = narrow_slot_shift(slot_span(tfirst, a, ntiles));
+                    const int shb = narrow_slot_shift(slot_span(tfirst, bt, ntiles));
+                    const uint32_t a0 = min(la >> sha, kSlots - 1), a1 = min(ha >> sha, kSlots - 1);
+                    const uint32_t b1 = min(hb >> shb, kSlots - 1);
+                    const bool try_a = rec_a && a1 - a0 <= 1, try_b = rec_b && b1 <= 1;
+                    sm[k][0] = try_a ? sa[a0] : 0xFFFFFFFFu, sm[k][1] = try_a ? sa[a1] : 0xFFFFFFFFu;
+                    sm[k][2] = try_b ? sb2[0] : 0xFFFFFFFFu, sm[k][3] = try_b ? sb2[b1] : 0xFFFFFFFFu;
+                }
             }
             R0[s][k] = r0;
             R1[s][k] = r1;
@@ -1837,6 +1917,7 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
     uint64_t dmax[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) dmax[k] = dfr.x[k] <= dfr.y[k] ? tiles_max(wt, dfr.x[k], dfr.y[k]) : 0;
+    if constexpr (kFast) commit(S - 1);
     {
         if (!lsn32) {  // the chunk's snapshot ranks: heads of all sub-chunks in one list
             const uint64_t le_mask = lane == 63 ? ~0ull : ((2ull << lane) - 1);
@@ -1899,7 +1980,8 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
         const uint32_t per = (ntiles + kLocTThreads - 1) / kLocTThreads;
         const uint32_t i0 = min(ntiles, threadIdx.x * per), i1 = min(ntiles, i0 + per);
         uint32_t sum = 0;
-        for (uint32_t i = i0; i < i1; ++i) sum += hist[i];
+        constexpr uint32_t kCount = kFast ? 0xFFFFu : 0xFFFFFFFFu;  // (a general shape's word is the count)
+        for (uint32_t i = i0; i < i1; ++i) sum += hist[i] & kCount;
         uint32_t x = sum;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -1911,10 +1993,15 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
         __syncthreads();
         uint32_t run = x - sum;
         for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) run += wtot[w];
-        uint32_t *row = work.cm + (size_t)g * ((ntiles + 3) & ~3u);
+        // (the fast shapes write two-word entries: the general ones drop
+        // nothing, located = kept, and keep the one-word table)
+        const size_t ro = (size_t)g * ((ntiles + 3) & ~3u);
         for (uint32_t i = i0; i < i1; ++i) {
-            const uint32_t c = hist[i];
-            row[i] = run << 16 | c;
+            const uint32_t h = hist[i], c = h & kCount;
+            if constexpr (kFast)
+                work.cmx[ro + i] = make_uint2(run << 16 | c, h >> 16);  // (located, before the filter)
+            else
+                work.cm[ro + i] = run << 16 | c;
             hist[i] = run;
             run += c;
         }
@@ -1945,6 +2032,18 @@ __global__ __launch_bounds__(kLocTThreads) void k_locate_t(NarrowView nv, WinVie
     HSC_STAMP(work, 0, 5);
 }
 
+// The window's shape: the fast instances are built for a batch with probes
+// over a bucket-table window of 1 or 2 words, no compressed codes, the last
+// word the last varying limb, ranks in lsn32 mode (W = 1 with a log table has
+// no instance: it takes the general one).
+bool narrow_locate_fast(const NarrowView &nv, const NarrowTiles &nt, const ProbeView &p)
+{
+    const int w = nv.W == 1 || nv.W == 2 ? nv.W : 0;
+    const bool tr = nt.trad != nullptr;
+    const bool log = tr && (nt.trad_shift & (int)kTradLog) != 0;
+    return tr && w != 0 && !nv.comp && nv.lw == nv.W && nt.rank_lsn32 && p.n > 0 && !(log && w == 1);
+}
+
 hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeView &p,
                            const ProbeWork &work, const NarrowTiles &nt, uint8_t *verdict,
                            hipStream_t s, int *shape)
@@ -1959,13 +2058,11 @@ hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeV
         return hipErrorInvalidValue;
     if (!nt.rank_lsn32 && nt.cdir.lds_n > (uint32_t)kDirLds) return hipErrorInvalidValue;
     const int w = nv.W == 1 || nv.W == 2 ? nv.W : 0;
-    // the window's shape: the fast instances are built for a batch with
-    // probes over a bucket-table window of 1 or 2 words, no compressed codes,
-    // the last word the last varying limb, ranks in lsn32 mode (W = 1 with a
-    // log table has no instance: it takes the general one)
     const bool log = tr && (nt.trad_shift & (int)kTradLog) != 0;
-    const bool fast = tr && w != 0 && !nv.comp && nv.lw == nv.W && nt.rank_lsn32 && p.n > 0 &&
-                      !(log && w == 1);
+    const bool fast = narrow_locate_fast(nv, nt, p);
+    // the table's layout is the caller's choice by the same rule: two-word
+    // entries (cmx) for a fast instance, one-word entries (cm) otherwise
+    if (fast ? !work.cmx || work.cm : !work.cm || work.cmx) return hipErrorInvalidValue;
     if (shape) *shape = fast ? 1 : 0;
 #define HSC_LOCATE(W_, TR_, ...)                                                                  \
     k_locate_t<W_, TR_, ##__VA_ARGS__><<<8 * ((work.G + 7) / 8), kLocTThreads, lds, s>>>(nv, wt, p, work, \
@@ -1996,8 +2093,11 @@ hipError_t launch_locate_t(const NarrowView &nv, const WinView &wt, const ProbeV
 uint32_t narrow_tiles_chunk() { return kLocTP * kLocTThreads; }
 uint32_t narrow_tiles_dir_lds() { return kDirLds; }
 
-// A tile of more than kTileCap records tells the host (ProbeWork::hot): every
-// such tile of a batch stores the same value, written through to host memory.
+// A tile that the locate's end-tile step gave more than kTileCap records --
+// located records, counted before the slot filter drops any (ProbeWork::cmx) --
+// tells the host (ProbeWork::hot): every such tile of a batch stores the same
+// value, written through to host memory.  The rounds and overflow items that
+// run are sized by the records the filter kept.
 __device__ __forceinline__ void mark_hot(const ProbeWork &work)
 {
     if (work.hot) __hip_atomic_store(work.hot, work.batch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -2016,6 +2116,9 @@ __device__ __forceinline__ void mark_hot(const ProbeWork &work)
 // pieces): one stream 62.1 vs 61.1 us, two streams 2.22 vs 2.17 G checks/s
 // (r02d) -- the headline is the two-stream number
 constexpr int kPlanSThreads = 512;  // a wave per tile
+// kWide: the table has two-word entries (work.cmx, a fast narrow locate);
+// else one-word entries (work.cm), located = kept, and no LDS for a second count
+template <bool kWide>
 __global__ __launch_bounds__(kPlanSThreads) void k_plan_s(ProbeWork work, uint32_t ntiles,
                                                           uint32_t *ctl, uint8_t *flags,
                                                           uint32_t n_txn, uint8_t *verdict)
@@ -2024,6 +2127,7 @@ __global__ __launch_bounds__(kPlanSThreads) void k_plan_s(ProbeWork work, uint32
     static_assert(TB % 4 == 0, "16-byte row pieces");
     constexpr uint32_t SR = kMaxChunks + 4;
     __shared__ __attribute__((aligned(16))) uint32_t sh[TB][SR];
+    __shared__ uint16_t shl[kWide ? TB : 1][kWide ? SR : 1];  // the located counts of the same entries
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint32_t t0 = blockIdx.x * TB, t = t0 + w;
     const uint32_t G = work.G, hs = hist_stride(G), rs = (ntiles + 3) & ~3u;
@@ -2031,8 +2135,17 @@ __global__ __launch_bounds__(kPlanSThreads) void k_plan_s(ProbeWork work, uint32
     for (uint32_t i = threadIdx.x; i < G * (TB / 4); i += kPlanSThreads) {
         const uint32_t g = i / (TB / 4), pc = i % (TB / 4);
         const uint32_t c = t0 + 4 * pc;
-        const u32x4 a = c < rs ? *(const u32x4 *)(work.cm + (size_t)g * rs + c) : u32x4{0, 0, 0, 0};
-        sh[4 * pc][g] = a.x, sh[4 * pc + 1][g] = a.y, sh[4 * pc + 2][g] = a.z, sh[4 * pc + 3][g] = a.w;
+        if constexpr (kWide) {  // two-word entries: 32 bytes per piece
+            const u32x4 *src = (const u32x4 *)(work.cmx + (size_t)g * rs + c);
+            const u32x4 z = {0, 0, 0, 0};
+            const u32x4 a = c < rs ? src[0] : z, b = c < rs ? src[1] : z;
+            sh[4 * pc][g] = a.x, sh[4 * pc + 1][g] = a.z, sh[4 * pc + 2][g] = b.x, sh[4 * pc + 3][g] = b.z;
+            shl[4 * pc][g] = (uint16_t)a.y, shl[4 * pc + 1][g] = (uint16_t)a.w;
+            shl[4 * pc + 2][g] = (uint16_t)b.y, shl[4 * pc + 3][g] = (uint16_t)b.w;
+        } else {
+            const u32x4 a = c < rs ? *(const u32x4 *)(work.cm + (size_t)g * rs + c) : u32x4{0, 0, 0, 0};
+            sh[4 * pc][g] = a.x, sh[4 * pc + 1][g] = a.y, sh[4 * pc + 2][g] = a.z, sh[4 * pc + 3][g] = a.w;
+        }
     }
     if (verdict) {
         // (a wave covers 64 consecutive read sets, 64-aligned: one bitmap word)
@@ -2048,12 +2161,13 @@ __global__ __launch_bounds__(kPlanSThreads) void k_plan_s(ProbeWork work, uint32
     __syncthreads();
     if (t >= ntiles) return;
     const uint32_t e = 8 * lane;
-    uint32_t v[8], c[8];
+    uint32_t v[8], c[8], located = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const uint32_t x = e + k < G ? sh[w][e + k] : 0;
         v[k] = x & 0xFFFFu;
         c[k] = x >> 16;
+        if constexpr (kWide) located += e + k < G ? shl[w][e + k] : 0;
     }
     uint32_t sum = 0;
 #pragma unroll
@@ -2083,8 +2197,15 @@ __global__ __launch_bounds__(kPlanSThreads) void k_plan_s(ProbeWork work, uint32
     }
     const uint32_t total = __shfl(x, 63, 64);
     if (lane == 0) work.counts[t] = total;
-    if (total > kTileCap) {  // hot tile: join items over its record numbers past kTileCap
-        if (lane == 0) mark_hot(work);
+    // the hot rule: located records (the tile's total where nothing is dropped)
+    if constexpr (kWide) {
+#pragma unroll
+        for (int o = 32; o; o >>= 1) located += __shfl_xor(located, o, 64);
+    } else {
+        located = total;
+    }
+    if (lane == 0 && located > kTileCap) mark_hot(work);
+    if (total > kTileCap) {  // join items over the kept records past kTileCap
         const uint32_t over = total - kTileCap;
         const uint32_t nx = (over + kJoinChunk - 1) / kJoinChunk;
         uint32_t ib = 0;
@@ -2101,8 +2222,12 @@ hipError_t launch_plan_s(const ProbeWork &work, uint32_t ntiles, uint32_t *ctl, 
 {
     if (ntiles == 0) return hipSuccess;
     constexpr uint32_t per = kPlanSThreads / 64;
-    k_plan_s<<<(ntiles + per - 1) / per, kPlanSThreads, 0, s>>>(work, ntiles, ctl, flags, n_txn,
-                                                                verdict);
+    if (work.cmx)
+        k_plan_s<true><<<(ntiles + per - 1) / per, kPlanSThreads, 0, s>>>(work, ntiles, ctl, flags, n_txn,
+                                                                          verdict);
+    else
+        k_plan_s<false><<<(ntiles + per - 1) / per, kPlanSThreads, 0, s>>>(work, ntiles, ctl, flags, n_txn,
+                                                                           verdict);
     return hipGetLastError();
 }
 
@@ -2183,14 +2308,22 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
         tile = sload(d), j0 = sload(d + 1), j1 = sload(d + 2);
     }
     const uint32_t G = work.G;
-    uint32_t e = 0, cs = 0;
+    uint32_t e = 0, cs = 0, el = 0;  // el: chunk g's located records of the tile
     // this block's share of the flags: the first stride's load goes out ahead
     // of the column's and the list's
     const uint32_t fstride = gridDim.x * kJoinThreads, fi = blockIdx.x * kJoinThreads + threadIdx.x;
     uint8_t f0 = 0;
     if constexpr (kMode == kJoinCol) {
         if (fi < work.n_txn) f0 = flags[fi];
-        if (threadIdx.x < G) e = work.cm[(size_t)threadIdx.x * rs + tile];
+        if (threadIdx.x < G) {
+            if (work.cmx) {  // one 8-byte load: both words of the entry
+                const uint2 ex = work.cmx[(size_t)threadIdx.x * rs + tile];
+                e = ex.x, el = ex.y;
+            } else {  // a general locate: located = kept
+                e = work.cm[(size_t)threadIdx.x * rs + tile];
+                el = e & 0xFFFFu;
+            }
+        }
     } else {
         const size_t col = (size_t)tile * hist_stride(G);
         if (threadIdx.x < G) {
@@ -2238,10 +2371,7 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
         }
         cs = e >> 16, e = run;
         j1 = __builtin_amdgcn_readfirstlane(total);
-        if (threadIdx.x == 0) {
-            work.counts[tile] = j1;  // (read back by the timing statistics)
-            if (j1 > kTileCap) mark_hot(work);
-        }
+        if (threadIdx.x == 0) work.counts[tile] = j1;  // (read back by the timing statistics)
     }
     if constexpr (kMode == kJoinTile) j1 = min(kTileCap, sload(work.counts + tile));
     if (kMode == kJoinCol || threadIdx.x < G) Es[threadIdx.x] = e, Cs[threadIdx.x] = cs;
@@ -2261,17 +2391,63 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
         maxima(lr, threadIdx.x, L.lb16, L.lb128);
         if (threadIdx.x < 2) L.vote[threadIdx.x] = 0;
     }
+    // the hot rule counts located records: their sum needs no scan and rides
+    // the list's barrier -- a second word per wave, read by thread 0 behind it
+    if constexpr (kMode == kJoinCol) {
+#pragma unroll
+        for (int o = 32; o; o >>= 1) el += __shfl_xor(el, o, 64);
+        if ((threadIdx.x & 63) == 0) wtot[kJoinThreads / 64 + (threadIdx.x >> 6)] = el;
+    }
     __syncthreads();
+    if constexpr (kMode == kJoinCol) {
+        if (threadIdx.x == 0) {
+            uint32_t located = 0;
+#pragma unroll
+            for (int w = 0; w < kJoinThreads / 64; ++w) located += wtot[kJoinThreads / 64 + w];
+            if (located > kTileCap) mark_hot(work);
+        }
+    }
     HSC_STAMP(work, 1, 1);
     const size_t area = 2 * (size_t)work.chunk;
+    // Record slot k of this thread in the round at jb (kNoRec: none).  A round
+    // of more than kJoinThreads records maps slot k to record jb + k *
+    // kJoinThreads + thread.  A smaller one -- what the locate's filter leaves
+    // of most tiles -- is dealt out as equal runs of consecutive records
+    // (eight of them from 128 records on, runs of kDealMin below), one per
+    // wave in slot 0 -- on the column path only (kJoinCol): the plan path's
+    // tile blocks and overflow items keep the thread-order mapping, which is
+    // what config 5's 33-record tiles ran faster with: in thread order its few records would
+    // all sit in wave 0, whose range-maximum passes the other seven waves
+    // would wait for at the barrier.  skip (wave-uniform): the wave's run of
+    // this slot is empty.
+    constexpr uint32_t kNoRec = 0xFFFFFFFFu;
+    // a wave's run is never shorter than 16 records while there are that many:
+    // wave_any_after32 resolves one range per 16-lane group and pass, so runs
+    // below 16 only add waves that walk (measured on config 2, two streams:
+    // 37.7-38.0 us with eight runs always, 36.8-37.1 with this floor)
+    constexpr uint32_t kDealMin = 16;
+    auto slot = [&](uint32_t jb, int k, bool &skip) -> uint32_t {
+        const uint32_t m = j1 > jb ? min(j1 - jb, (uint32_t)kJoinChunk) : 0;  // block-uniform
+        if (kMode == kJoinCol && m <= (uint32_t)kJoinThreads) {
+            const uint32_t per = max((m + kJoinThreads / 64 - 1) / (kJoinThreads / 64), kDealMin);  // <= 64
+            const uint32_t w0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * per;
+            const uint32_t lane = threadIdx.x & 63;
+            skip = k > 0 || w0 >= m;
+            return !skip && lane < per && w0 + lane < m ? jb + w0 + lane : kNoRec;
+        }
+        const uint32_t j = jb + k * kJoinThreads + threadIdx.x;
+        skip = __builtin_amdgcn_readfirstlane(j) >= j1;
+        return j < j1 ? j : kNoRec;
+    };
     // a round's record loads: records jb .. jb + kJoinChunk of the tile
     auto fetch = [&](uint32_t jb) {
 #pragma unroll
         for (int k = 0; k < kRec; ++k) {
-            const uint32_t j = jb + k * kJoinThreads + threadIdx.x;
-            // a wave past the item's records has nothing to search or load (walk
-            // skips it the same way; the vote reads its records as empty)
-            if (__builtin_amdgcn_readfirstlane(j) >= j1) {
+            bool skip;
+            const uint32_t j = slot(jb, k, skip);
+            // a wave with no record in this slot has nothing to search or load
+            // (walk skips it the same way; the vote reads its records as empty)
+            if (skip) {
                 rec[k] = u32x4{0, 0, 0, 0};
                 continue;
             }
@@ -2281,8 +2457,8 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
                 const uint32_t c = g + (1u << b);
                 if (c < G && Es[c] <= j) g = c;
             }
-            rec[k] = j < j1 ? *(const u32x4 *)(nt.recs + g * area + Cs[g] + (j - Es[g]))
-                            : u32x4{0, 0, 0, 0};
+            rec[k] = j != kNoRec ? *(const u32x4 *)(nt.recs + g * area + Cs[g] + (j - Es[g]))
+                                 : u32x4{0, 0, 0, 0};
         }
     };
     // the whole tile: rows and maxima to LDS as they lie (today's staging)
@@ -2314,10 +2490,11 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
         constexpr uint32_t N = 1u << LV;
 #pragma unroll
         for (int k = 0; k < kRec; ++k) {
-            const uint32_t j = r0 + k * kJoinThreads + threadIdx.x;
-            // a wave past the item's records skips the round as a whole; inside,
-            // j < j1 is a predicate (the range maxima are resolved by the wave)
-            if (__builtin_amdgcn_readfirstlane(j) >= j1) continue;
+            bool skip;
+            const uint32_t j = slot(r0, k, skip);
+            // a wave with no record in this slot skips it as a whole; inside, a
+            // lane's record is a predicate (the range maxima are resolved by the wave)
+            if (skip) continue;
             const uint32_t lo = rec[k].x, hi = rec[k].y, rs = rec[k].z;
             uint32_t ja = 1, jb = 1;
 #pragma unroll
@@ -2329,7 +2506,7 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
             const uint32_t kl = keys[0];
             const uint32_t pa = min(ja - N + (kl < lo), nrow);
             const uint32_t pb = min(jb - N + (kl <= hi), nrow);
-            if (wave_any_after32(rank, b16, b128, pa, pb, rs, j < j1 && pa < pb)) {
+            if (wave_any_after32(rank, b16, b128, pa, pb, rs, j != kNoRec && pa < pb)) {
                 // (r05w, world-1 per-rank step: these atomics 50.7 / 51.9 us per
                 // step, guarded by a read of the verdict byte 53.3 / 52.5, the
                 // pack pass instead 52.7 / 51.9 -- the same within the spread)
@@ -2346,8 +2523,10 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
             // a live record whose snapshot is older than a row left out of the list?
             bool old = false;
 #pragma unroll
-            for (int k = 0; k < kRec; ++k)
-                old |= jb + k * kJoinThreads + threadIdx.x < j1 && rec[k].x <= rec[k].y && rec[k].z < theta;
+            for (int k = 0; k < kRec; ++k) {
+                bool skip;
+                old |= slot(jb, k, skip) != kNoRec && rec[k].x <= rec[k].y && rec[k].z < theta;
+            }
             // (a slot per round parity: a wave already in the next round's vote
             // must not change what a slower wave still has to read of this one's)
             uint32_t *vote = L.vote + (jb / kJoinChunk & 1);
@@ -2396,7 +2575,7 @@ __global__ __launch_bounds__(kJoinThreads) __attribute__((amdgpu_waves_per_eu(8,
     // chunk share lines of its record area, which that XCD's L2 then serves)
     const uint32_t tb = join_tile_blocks(ntiles);
     if constexpr (kCol) {
-        __shared__ uint32_t wtot[kJoinThreads / 64];
+        __shared__ uint32_t wtot[2 * (kJoinThreads / 64)];  // kept and located, per wave
         const uint32_t tile = xcd_chunk(blockIdx.x, tb / 8);
         if (tile < ntiles) {
             join_s_item<kJoinCol>(work, nt, n, tile, verdict, L,
@@ -2436,7 +2615,7 @@ hipError_t launch_join_t(const ProbeWork &work, const NarrowTiles &nt, uint32_t 
 hipError_t launch_join_col(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,
                            uint32_t ntiles, uint8_t *flags, hipStream_t s)
 {
-    if (n == 0 || ntiles == 0 || !work.vout || work.G > (uint32_t)kMaxChunks) return hipErrorInvalidValue;
+    if (n == 0 || ntiles == 0 || !work.vout || (!work.cmx && !work.cm) || work.G > (uint32_t)kMaxChunks) return hipErrorInvalidValue;
     k_join_t<true><<<join_tile_blocks(ntiles), kJoinThreads, 0, s>>>(work, nt, n, ntiles, work.vout, flags);
     return hipGetLastError();
 }

@@ -472,8 +472,10 @@ int hsc_small_stats(hsc_ctx *ctx, hsc_small_stats_t *out);
  * chunk's verdicts (device time + transfers not hidden behind the next
  * chunk's marshal).  column_batches / plan_batches: dense batches over a
  * narrow window whose join scanned its tiles' columns itself / that ran the
- * plan kernel first (a batch with a tile of more than 1024 records sends the
- * next 64 down the plan path).  fast_locates / general_locates: launches of
+ * plan kernel first.  The rule, stated once: a batch is concentrated when
+ * some tile received more than 1024 located records -- the records the
+ * locate's end-tile step gave the tile, counted before any filter drops one --
+ * and a concentrated batch sends the next 64 down the plan path.  fast_locates / general_locates: launches of
  * the narrow-tile locate by instance -- one built for the window's shape (1
  * or 2 key words, the last one varying, bucket table, no compressed codes,
  * 32-bit commit ranks) / the one that reads the shape at run time.

@@ -614,7 +614,9 @@ struct hsc_ctx {
     DBuf d_commits, d_cdir, d_tdir, d_trad, d_done, w_vflags, d_key32, d_rank32, d_ctmp[4];
     DBuf d_recent;     // the tiles' recent lists and slot tables (narrow_recent_build), built with d_key32 / d_rank32
     int slot_qshift = 0;  // the slot tables' quantum (NarrowTiles::qshift), set with them
-    DBuf d_fulljoins;  // u32: join blocks / items that staged a whole tile (hsc_batch_stats); every lane adds to it
+    // u32[2]: join blocks / items that staged a whole tile (hsc_batch_stats; every lane adds
+    // to it), tiles k_join_w left to the block-wide join (hsc_join_stats)
+    DBuf d_fulljoins;
     Dir16 cdir{}, tdir{};
     uint32_t trad_m = 0;       // tile bucket table size (0: none)
     bool trad_log = false;     // the table is in log mode (narrow_trad_pick)
@@ -627,11 +629,18 @@ struct hsc_ctx {
     // narrow tiles, the path of a batch (probe_ntiles): without a plan -- the
     // join scans its tile's column itself -- unless a batch of the last
     // kHotBatches had a tile of more than kTileCap records, which the kernels
-    // report by storing the batch's number (nt_batch, from 1) into h_hot, a
-    // mapped host word read without synchronising
+    // report by storing the batch's number (nt_batch, from 1) into h_hot[0], a
+    // mapped host word read without synchronising.
+    // The column path's join: a wave per tile (k_join_w) unless the locate was
+    // a general instance or a batch of the last kHotBatches was wide -- a
+    // block left kWideBlock or more of its 8 tiles to the block-wide join and
+    // stored the batch's number into h_hot[1], the second word of the same
+    // allocation (a context's first dense batch pays for one mapped
+    // allocation, not two), read the same way
     static constexpr uint64_t kHotBatches = 64;
     HBuf h_hot;
     uint64_t nt_batch = 0;
+    std::atomic<uint64_t> nt_wave{0}, nt_block{0};  // column batches per join kernel
     std::atomic<uint64_t> nt_column{0}, nt_plan{0};  // batches per path (hsc_batch_stats)
     std::atomic<uint64_t> nt_fast{0}, nt_general{0};  // locate launches per instance class
     DBuf d_gid, d_words, d_lsn, d_gid2, d_words2, d_lsn2, d_flags, d_scratch;

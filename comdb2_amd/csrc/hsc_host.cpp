@@ -2600,10 +2600,11 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
     ntl.recs = c->w_trecs.as<uint4>();
     narrow_recent_view(ntl, c->d_recent.as<uint32_t>(), wn.ntiles, c->slot_qshift);
     if (!c->d_fulljoins.p) {
-        HIPCHK(c, c->d_fulljoins.ensure(4));
-        HIPCHK(c, hipMemset(c->d_fulljoins.p, 0, 4));
+        HIPCHK(c, c->d_fulljoins.ensure(8));
+        HIPCHK(c, hipMemset(c->d_fulljoins.p, 0, 8));
     }
     work.full_joins = c->d_fulljoins.as<uint32_t>();
+    work.wave_fallbacks = work.full_joins + 1;
     // conflict flags: internal, all zero between batches (the pack clears them)
     const size_t had = c->w_vflags.bytes;
     HIPCHK(c, c->w_vflags.ensure((std::max<size_t>(b->n_txn, 1) + 15) & ~(size_t)15));
@@ -2621,11 +2622,13 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
     const bool delta = pack_after_delta(c);
     bool column = false;
     if (joins) {
-        if (!c->h_hot.p) {
-            if (c->h_hot.ensure(8, true, true)) return fail(c, HSC_ENOMEM, "hot word");
-            *c->h_hot.as<volatile uint64_t>() = 0;
+        if (!c->h_hot.p) {  // two words: hot, wide (hsc_ctx.h)
+            if (c->h_hot.ensure(16, true, true)) return fail(c, HSC_ENOMEM, "hot word");
+            c->h_hot.as<volatile uint64_t>()[0] = 0;
+            c->h_hot.as<volatile uint64_t>()[1] = 0;
         }
         work.hot = (uint64_t *)c->h_hot.dp;
+        work.wide = work.hot + 1;
         work.batch = ++c->nt_batch;
         const uint64_t hot = *c->h_hot.as<volatile uint64_t>();
         column = !c->trad_log && !(hot && work.batch - hot <= hsc_ctx::kHotBatches);
@@ -2655,7 +2658,16 @@ static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
         // (no plan, no scatter: their legs of the timing are empty)
         if (tm) HIPCHK(c, hipEventRecord(c->ev[2], s));
         if (tm) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        HIPCHK(c, launch_join_col(work, ntl, wn.n, wn.ntiles, flags, s));
+        // a wave per tile for what a fast locate's filter left, unless a batch
+        // of the last kHotBatches was wide (the word as it stands: a late
+        // store only delays the switch, both joins give the same verdicts)
+        const uint64_t wide = c->h_hot.as<volatile uint64_t>()[1];
+        const bool wave = work.cmx && !(wide && work.batch - wide <= hsc_ctx::kHotBatches);
+        (wave ? c->nt_wave : c->nt_block)++;
+        if (wave)
+            HIPCHK(c, launch_join_wave(work, ntl, wn.n, wn.ntiles, flags, s));
+        else
+            HIPCHK(c, launch_join_col(work, ntl, wn.n, wn.ntiles, flags, s));
         if (tm) HIPCHK(c, hipEventRecord(c->ev[4], s));
         HIPCHK_RC(c, probe_delta(c, b->verdict));
         if (delta) HIPCHK(c, launch_pack(b->verdict, (uint32_t)b->n_txn, b->bitmap, s));
@@ -4501,6 +4513,21 @@ int hsc_batch_stats(hsc_ctx *c, hsc_batch_stats_t *out)
         if (hipMemcpy(&full, c->d_fulljoins.p, 4, hipMemcpyDeviceToHost) != hipSuccess) full = 0;
     }
     out->full_tile_joins = full;
+    return HSC_OK;
+}
+
+int hsc_join_stats(hsc_ctx *c, hsc_join_stats_t *out)
+{
+    if (!c || !out) return HSC_EINVAL;
+    out->wave_batches = c->nt_wave.load();
+    out->block_batches = c->nt_block.load();
+    // the device counter as it stands (a batch still running may yet add to it)
+    uint32_t fell = 0;
+    if (c->d_fulljoins.p) {
+        (void)hipSetDevice(c->device);
+        if (hipMemcpy(&fell, c->d_fulljoins.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost) != hipSuccess) fell = 0;
+    }
+    out->wave_fallback_tiles = fell;
     return HSC_OK;
 }
 

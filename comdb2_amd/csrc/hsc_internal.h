@@ -72,6 +72,8 @@ constexpr int kDirectPerTile = 8;   // narrow: direct probe below 8 ranges per t
 constexpr int kJoinThreads = 512;
 constexpr int kJoinChunk = 1024;    // join records per workgroup
 constexpr uint32_t kTileCap = 1024; // narrow tiles: records per tile bucket before it spills
+constexpr uint32_t kWaveCap = 128;  // narrow tiles: kept records of a tile that one wave joins (k_join_w)
+constexpr uint32_t kWideBlock = 3;  // k_join_w: tiles of a block's 8 left to the block that make a batch wide
 constexpr int kLdsJoinBudget = 65536;
 
 // Probe codes written by the locate kernel: a | b << 31 | kind << 62.
@@ -265,6 +267,12 @@ struct ProbeWork {
     // narrow join: blocks / items that staged a whole tile, not its recent list
     // (cumulative, device memory; null: not counted)
     uint32_t *full_joins;
+    // the wave-per-tile join (k_join_w): tiles it left to the whole block
+    // (cumulative, device memory; null: not counted), and the word of mapped
+    // host memory a block that left kWideBlock tiles or more stores `batch`
+    // into, read by the host as `hot` is (null: none)
+    uint32_t *wave_fallbacks;
+    uint64_t *wide;
 };
 // Diagnostic phase stamps (HSC_STAMPS builds only): thread 0 of a block
 // records s_memtime at phase boundaries into a buffer of its own (never an
@@ -563,6 +571,12 @@ hipError_t launch_join_t(const ProbeWork &work, const NarrowTiles &nt, uint32_t 
 // locate's flags into the verdict bytes (and bitmap), clearing them.
 hipError_t launch_join_col(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,
                            uint32_t ntiles, uint8_t *flags, hipStream_t s);
+// The same join for a fast locate's two-word table (work.cmx), a wave per
+// tile and 8 tiles per block: tiles of more than kWaveCap kept records, or
+// with a snapshot older than their recent list, are joined by the whole block
+// in the same launch, as launch_join_col's blocks join them.
+hipError_t launch_join_wave(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,
+                            uint32_t ntiles, uint8_t *flags, hipStream_t s);
 // Dependency graph + SCC (hsc_graph.hip).
 constexpr uint64_t kDepWW = 1, kDepWR = 2, kDepRW = 4;
 constexpr uint64_t kDepRT = 8;  // real-time order (hsc_realtime.hip): staged only, never from ops

@@ -2272,6 +2272,20 @@ __device__ __forceinline__ void move_flag(const ProbeWork &work, uint8_t *flags,
     }
 }
 
+// The strides of a block's share past the first (a batch of more read sets
+// than the grid has threads): four loads in flight.
+__device__ __forceinline__ void move_flags_rest(const ProbeWork &work, uint8_t *flags, uint8_t *verdict,
+                                                uint32_t fi, uint32_t fstride)
+{
+    for (size_t i = (size_t)fi + fstride; i < work.n_txn; i += 4 * (size_t)fstride) {
+        uint8_t f[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) f[k] = i + (size_t)k * fstride < work.n_txn ? flags[i + (size_t)k * fstride] : 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) move_flag(work, flags, verdict, (uint32_t)(i + (size_t)k * fstride), f[k]);
+    }
+}
+
 // The rows a join block stages.  Exactness rule of the recent list (k_recent):
 // if r(S) >= rtheta[t], every row of tile t with rank32 > r(S) is a list
 // member -- a row left out has rank32 <= rtheta[t] <= r(S), ties included --
@@ -2288,7 +2302,9 @@ struct JoinLds {
     uint32_t *Es, *Cs, *vote;  // vote[2]: a round's "stage the whole tile"
 };
 
-template <JoinMode kMode>
+// kMove (kJoinCol): the block moves its share of the locate's flags here;
+// k_join_w's blocks have moved theirs before they call this for a tile
+template <JoinMode kMode, bool kMove = true>
 __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowTiles &nt,
                                             uint32_t n, uint32_t xi, uint8_t *verdict,
                                             const JoinLds &L,
@@ -2314,7 +2330,7 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
     const uint32_t fstride = gridDim.x * kJoinThreads, fi = blockIdx.x * kJoinThreads + threadIdx.x;
     uint8_t f0 = 0;
     if constexpr (kMode == kJoinCol) {
-        if (fi < work.n_txn) f0 = flags[fi];
+        if (kMove && fi < work.n_txn) f0 = flags[fi];
         if (threadIdx.x < G) {
             if (work.cmx) {  // one 8-byte load: both words of the entry
                 const uint2 ex = work.cmx[(size_t)threadIdx.x * rs + tile];
@@ -2341,14 +2357,9 @@ __device__ __forceinline__ void join_s_item(const ProbeWork &work, const NarrowT
     }
     u32x4 rec[kRec];
     if constexpr (kMode == kJoinCol) {
-        move_flag(work, flags, verdict, fi, f0);
-        // (a batch of more read sets than the grid has threads: four loads in flight)
-        for (size_t i = (size_t)fi + fstride; i < work.n_txn; i += 4 * (size_t)fstride) {
-            uint8_t f[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) f[k] = i + (size_t)k * fstride < work.n_txn ? flags[i + (size_t)k * fstride] : 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) move_flag(work, flags, verdict, (uint32_t)(i + (size_t)k * fstride), f[k]);
+        if constexpr (kMove) {
+            move_flag(work, flags, verdict, fi, f0);
+            move_flags_rest(work, flags, verdict, fi, fstride);
         }
         // block-exclusive scan of the column's counts: wave scans, then the
         // 8 wave totals through LDS
@@ -2609,6 +2620,244 @@ hipError_t launch_join_t(const ProbeWork &work, const NarrowTiles &nt, uint32_t 
     // that prefetch their next tile -- 27.8 vs 32 us on config 2)
     const uint32_t blocks = join_tile_blocks(ntiles) + std::min<uint32_t>(max_items - ntiles, extra_blocks);
     k_join_t<false><<<blocks, kJoinThreads, 0, s>>>(work, nt, n, ntiles, verdict, nullptr);
+    return hipGetLastError();
+}
+
+// ---- join: a wave per tile ----
+// What the locate's slot filter leaves of most tiles is a few dozen records,
+// of which a 512-thread block is mostly barrier.  Here a block serves 8
+// consecutive tiles, one per wave.  Prologue, as k_plan_s<true>: the 64-byte
+// pieces of the 8 tiles' entries of every chunk row (coalesced) transposed
+// into LDS, the block's share of the flag move, and each wave's list -- a quad
+// of keys and one of ranks per lane -- into an LDS area of the wave's own; one
+// barrier.  Then every wave on its own: scan of its column (8 entries a
+// lane), counts[tile], the hot rule, and for a tile of at most kWaveCap kept
+// records (two per lane) the chunk search, the record gather, the list vote
+// by ballot and the 8-level walk.  The scan leaves {run start << 16 |
+// exclusive offset} in the column's LDS words: 16 bits of offset, read only
+// where the total is <= kWaveCap.
+// A tile of more records, or one whose vote fails, is left alone: its wave
+// sets a bit of a block-shared mask, and behind a second barrier the whole
+// block runs join_s_item<kJoinCol> for each such tile in turn (its flag move
+// off), in LDS that aliases the wave phase's.  A block that falls back for
+// kWideBlock tiles or more stores the batch's number into work.wide (the rule
+// in hip_serial.h: the next kHotBatches batches take k_join_t<true>).
+// LDS: max(wave phase 41,792 B, block phase 40,224 B) + 4: three blocks a CU.
+constexpr int kJoinWTiles = kJoinThreads / 64;
+constexpr uint32_t kJoinWRow = kMaxChunks + 4;  // a column's words in LDS
+constexpr uint32_t kJoinWList = 2 * kRecent + kRecent / 16 + 4;  // a wave's list: keys, ranks, maxima
+static_assert(kWaveCap == 2 * 64, "two record slots per lane");
+static_assert(kMaxChunks == 8 * 64, "a wave scans a column, 8 entries per lane");
+static_assert(kJoinWTiles == 8, "64-byte row pieces, a bit per tile");
+
+__host__ __device__ inline uint32_t join_wave_blocks(uint32_t ntiles)
+{
+    return 8 * (((ntiles + kJoinWTiles - 1) / kJoinWTiles + 7) / 8);
+}
+
+__global__ __launch_bounds__(kJoinThreads) void k_join_w(ProbeWork work, NarrowTiles nt, uint32_t n,
+                                                         uint32_t ntiles, uint8_t *verdict,
+                                                         uint8_t *flags)
+{
+    constexpr uint32_t T = 1u << kTLog2;
+    constexpr int TB = kJoinWTiles;
+    constexpr uint32_t SR = kJoinWRow;
+    constexpr uint32_t kWaveWords = TB * SR + TB * kJoinWList + TB * SR / 2;
+    constexpr uint32_t kBlockWords = 2 * T + T / 16 + T / 128 + 2 * kRecent + kRecent / 16 + 4 +
+                                     2 * kMaxChunks + 4 + 2 * (kJoinThreads / 64);
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kWaveWords > kBlockWords ? kWaveWords : kBlockWords];
+    __shared__ uint32_t fell;  // bit w: tile t0 + w is left to the block
+    // the wave phase
+    uint32_t *const sh = lds;                                        // [TB][SR] kept: run start << 16 | count
+    uint32_t *const lists = lds + TB * SR;                           // [TB][kJoinWList]
+    uint16_t *const shl = (uint16_t *)(lds + TB * SR + TB * kJoinWList);  // [TB][SR] located
+    const uint32_t lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    HSC_STAMP(work, 1, 0);
+    // neighbouring groups on one XCD, as the tile join's tiles
+    const uint32_t t0 = TB * xcd_chunk(blockIdx.x, gridDim.x / 8), t = t0 + w;
+    const uint32_t G = work.G, rs = (ntiles + 3) & ~3u;
+    const uint32_t fstride = gridDim.x * kJoinThreads, fi = blockIdx.x * kJoinThreads + threadIdx.x;
+    // loads first: the first stride's flag, the row pieces (16 bytes: the
+    // entries of two tiles), the list
+    const uint8_t f0 = fi < work.n_txn ? flags[fi] : 0;
+    constexpr int kPieces = kMaxChunks * (TB / 2) / kJoinThreads;  // 4
+    u32x4 pc[kPieces];
+#pragma unroll
+    for (int k = 0; k < kPieces; ++k) {
+        const uint32_t i = threadIdx.x + k * kJoinThreads, g = i / (TB / 2), c = t0 + 2 * (i % (TB / 2));
+        pc[k] = g < G && c < rs ? *(const u32x4 *)(work.cmx + (size_t)g * rs + c) : u32x4{0, 0, 0, 0};
+    }
+    uint32_t *const lkeys = lists + w * kJoinWList, *const lrank = lkeys + kRecent;
+    uint32_t *const lb16 = lrank + kRecent, *const lb128 = lb16 + kRecent / 16;
+    u32x4 lk = {0, 0, 0, 0}, lr = {0, 0, 0, 0};
+    uint32_t theta = 0;
+    if (t < ntiles) {
+        const size_t q = (size_t)t * kRecent + 4 * lane;
+        lk = *(const u32x4 *)(nt.rkey32 + q);
+        lr = *(const u32x4 *)(nt.rrank32 + q);
+        theta = sload(nt.rtheta + t);
+    }
+    move_flag(work, flags, verdict, fi, f0);
+    move_flags_rest(work, flags, verdict, fi, fstride);
+    if (t0 >= ntiles) return;  // (block-uniform) a block past the tiles: its flags only
+#pragma unroll
+    for (int k = 0; k < kPieces; ++k) {
+        const uint32_t i = threadIdx.x + k * kJoinThreads, g = i / (TB / 2), c = 2 * (i % (TB / 2));
+        if (g < G) {
+            sh[c * SR + g] = pc[k].x, sh[(c + 1) * SR + g] = pc[k].z;
+            shl[c * SR + g] = (uint16_t)pc[k].y, shl[(c + 1) * SR + g] = (uint16_t)pc[k].w;
+        }
+    }
+    ((u32x4 *)lkeys)[lane] = lk;
+    ((u32x4 *)lrank)[lane] = lr;
+    {  // the ranks' 16-row maxima (4 lanes) and 128-row maxima (32 lanes)
+        uint32_t m = max(max(lr.x, lr.y), max(lr.z, lr.w));
+        m = max(m, (uint32_t)__shfl_xor((int)m, 1, 64));
+        m = max(m, (uint32_t)__shfl_xor((int)m, 2, 64));
+        if ((lane & 3) == 0) lb16[lane >> 2] = m;
+#pragma unroll
+        for (int d = 4; d < 32; d <<= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+        if ((lane & 31) == 0) lb128[lane >> 5] = m;
+    }
+    if (threadIdx.x == 0) fell = 0;
+    __syncthreads();
+    HSC_STAMP(work, 1, 1);
+    if (t < ntiles) {
+        uint32_t *const col = sh + w * SR;
+        const uint16_t *const lcol = shl + w * SR;
+        const uint32_t e = 8 * lane;
+        uint32_t v[8], c[8], located = 0, sum = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t x = e + k < G ? col[e + k] : 0;
+            v[k] = x & 0xFFFFu;
+            c[k] = x >> 16;
+            located += e + k < G ? lcol[e + k] : 0;
+            sum += v[k];
+        }
+        uint32_t x = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+#pragma unroll
+        for (int o = 32; o; o >>= 1) located += __shfl_xor(located, o, 64);
+        const uint32_t total = __builtin_amdgcn_readfirstlane(__shfl(x, 63, 64));
+        if (lane == 0) work.counts[t] = total;  // (read back by the timing statistics)
+        if (lane == 0 && located > kTileCap) mark_hot(work);
+        bool fall = total > kWaveCap;  // wave-uniform
+        if (!fall && total) {
+            uint32_t run = x - sum;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (e + k < G) col[e + k] = c[k] << 16 | run;
+                run += v[k];
+            }
+            // (the wave's own LDS words: written above, searched below by other lanes)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const size_t area = 2 * (size_t)work.chunk;
+            u32x4 rec[2];
+            bool old = false;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const uint32_t j = 64 * k + lane;
+                rec[k] = u32x4{0, 0, 0, 0};
+                if (64u * k >= total) continue;
+                uint32_t g = 0;  // offset 0 <= j
+#pragma unroll
+                for (int b = 8; b >= 0; --b) {
+                    const uint32_t cg = g + (1u << b);
+                    if (cg < G && (col[cg < G ? cg : 0] & 0xFFFFu) <= j) g = cg;
+                }
+                if (j < total) {
+                    const uint32_t eg = col[g];
+                    rec[k] = *(const u32x4 *)(nt.recs + g * area + (eg >> 16) + (j - (eg & 0xFFFFu)));
+                }
+                // a live record whose snapshot is older than a row left out of the list?
+                old |= j < total && rec[k].x <= rec[k].y && rec[k].z < theta;
+            }
+            fall = __ballot(old) != 0;
+            HSC_STAMP(work, 1, 2);
+            if (!fall) {
+                constexpr uint32_t N = kRecent;
+                const uint32_t nrow = min(kRecent, min(T, n - (t << kTLog2)));
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    if (64u * k >= total) continue;
+                    const uint32_t lo = rec[k].x, hi = rec[k].y;
+                    uint32_t ja = 1, jb = 1;
+#pragma unroll
+                    for (int d = 0; d < kRecentLog2; ++d) {
+                        const uint32_t ka = lkeys[ja], kb = lkeys[jb];
+                        ja = 2 * ja + (ka < lo);
+                        jb = 2 * jb + (kb <= hi);
+                    }
+                    const uint32_t kl = lkeys[0];
+                    const uint32_t pa = min(ja - N + (kl < lo), nrow);
+                    const uint32_t pb = min(jb - N + (kl <= hi), nrow);
+                    // A range of at most kShort list rows is read by its own
+                    // lane, all of them in one LDS round trip; the wave resolves
+                    // only the longer ones, four a pass (stamps on config 2:
+                    // a tile's ~50 records nearly all reach the passes
+                    // otherwise -- the list's rows are the newest, so their
+                    // 16-row maxima pass the two-read filter -- and the walk
+                    // phase takes 8.3k cycles of the wave's 19k)
+                    constexpr uint32_t kShort = 4;
+                    const bool live = 64 * k + lane < total && pa < pb;
+                    const bool brief = live && pb - pa <= kShort;
+                    bool hit = false;
+#pragma unroll
+                    for (uint32_t i = 0; i < kShort; ++i) {
+                        const bool in = brief && pa + i < pb;
+                        hit |= in & (lrank[in ? pa + i : 0] > rec[k].z);
+                    }
+                    hit |= wave_any_after32(lrank, lb16, lb128, pa, pb, rec[k].z, live && !brief);
+                    if (hit) {
+                        verdict[rec[k].w] = 1;
+                        if (work.bitmap)
+                            atomicOr((unsigned long long *)&work.bitmap[rec[k].w >> 6], 1ull << (rec[k].w & 63));
+                    }
+                }
+            }
+        }
+        if (fall && lane == 0) atomicOr(&fell, 1u << w);
+    }
+    HSC_STAMP(work, 1, 3);  // (wave 0: its tile's walks are done)
+    __syncthreads();
+    uint32_t todo = __builtin_amdgcn_readfirstlane(fell);
+    if (!todo) return;
+    if (threadIdx.x == 0) {
+        const uint32_t nfell = __popc(todo);
+        if (work.wave_fallbacks) atomicAdd(work.wave_fallbacks, nfell);
+        if (nfell >= kWideBlock && work.wide)
+            __hip_atomic_store(work.wide, work.batch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    // the block phase, over the wave phase's LDS
+    uint32_t *o = lds;
+    auto take = [&o](uint32_t words) {
+        uint32_t *p = o;
+        o += words;
+        return p;
+    };
+    JoinLds L;
+    L.keys = take(T), L.rank = take(T), L.b16 = take(T / 16), L.b128 = take(T / 128);
+    L.lkeys = take(kRecent), L.lrank = take(kRecent), L.lb16 = take(kRecent / 16), L.lb128 = take(4);
+    L.Es = take(kMaxChunks), L.Cs = take(kMaxChunks), L.vote = take(4);
+    uint32_t *const wtot = take(2 * (kJoinThreads / 64));
+    for (bool first = true; todo; todo &= todo - 1, first = false) {
+        if (!first) __syncthreads();  // the previous tile's LDS reads are done
+        join_s_item<kJoinCol, false>(work, nt, n, t0 + (__ffs(todo) - 1), verdict, L, rs, flags, wtot);
+    }
+}
+
+hipError_t launch_join_wave(const ProbeWork &work, const NarrowTiles &nt, uint32_t n,
+                            uint32_t ntiles, uint8_t *flags, hipStream_t s)
+{
+    if (n == 0 || ntiles == 0 || !work.vout || !work.cmx || work.G > (uint32_t)kMaxChunks) return hipErrorInvalidValue;
+    k_join_w<<<join_wave_blocks(ntiles), kJoinThreads, 0, s>>>(work, nt, n, ntiles, work.vout, flags);
     return hipGetLastError();
 }
 

@@ -238,6 +238,10 @@ class BatchStats(C.Structure):
                                           "full_tile_joins")]
 
 
+class JoinStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("wave_batches", "block_batches", "wave_fallback_tiles")]
+
+
 class ProtocolTxn(C.Structure):
     """hsc_protocol_txn: one txn of the commit-protocol harness."""
     _fields_ = [("arr", _p), ("writes", _p), ("nwrites", C.c_int)]
@@ -290,7 +294,7 @@ EXPORTS = [
     "hsc_multi_marshal_routed", "hsc_multi_routed_member", "hsc_multi_enable_timing",
     "hsc_multi_member_probe_ms", "hsc_multi_route_stats", "hsc_multi_graph_scc",
     "hsc_multi_graph_phase_ms",
-    "hsc_marshal_arrs", "hsc_batch_stats", "hsc_regop_stats", "hsc_harness_commit_protocol",
+    "hsc_marshal_arrs", "hsc_batch_stats", "hsc_join_stats", "hsc_regop_stats", "hsc_harness_commit_protocol",
     "hsc_multi_set_mode", "hsc_multi_mode", "hsc_multi_routed_phase_stats",
 ]
 MULTI_AUTO, MULTI_PIECES, MULTI_REPLICAS = 0, 1, 2
@@ -409,6 +413,7 @@ def load() -> C.CDLL:
                                                   _p, _p, C.POINTER(ProtocolResult)]),
         "hsc_window_layout": (C.c_int, [_p]),
         "hsc_batch_stats": (C.c_int, [_p, C.POINTER(BatchStats)]),
+        "hsc_join_stats": (C.c_int, [_p, C.POINTER(JoinStats)]),
         "hsc_marshal_arrs": (C.c_int, [_p, C.POINTER(_p), _p, C.c_int,
                                        C.POINTER(C.POINTER(Marshalled))]),
         "hsc_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, ctx_pp]),
@@ -858,6 +863,13 @@ class Validator:
         self._chk(self.lib.hsc_batch_stats(self.ctx, C.byref(st)), "hsc_batch_stats")
         d = {k: getattr(st, k) for k, _ in BatchStats._fields_}
         return {k: (v / 1e6 if k.endswith("_ns") else v) for k, v in d.items()}
+
+    def join_stats(self) -> dict:
+        """Column batches per join kernel and the tiles the wave-per-tile join
+        left to a whole block (hsc_join_stats)."""
+        st = JoinStats()
+        self._chk(self.lib.hsc_join_stats(self.ctx, C.byref(st)), "hsc_join_stats")
+        return {k: getattr(st, k) for k, _ in JoinStats._fields_}
 
     def small_stats(self) -> dict:
         """Small-batch path phase totals (hsc_small_stats): calls and the mean

@@ -491,6 +491,22 @@ typedef struct hsc_batch_stats_t {
     uint64_t full_tile_joins;
 } hsc_batch_stats_t;
 int hsc_batch_stats(hsc_ctx *ctx, hsc_batch_stats_t *out);
+/* The join kernel of the column batches (column_batches above), since the
+ * context was created.  wave_batches: joined a wave per tile, 8 tiles per
+ * block; block_batches: joined a 512-thread block per tile; their sum is
+ * column_batches.  A wave joins a tile of at most 128 records that the
+ * locate's filter kept, all answered from the tile's recent list; any other
+ * tile falls back to the whole block, in the same launch
+ * (wave_fallback_tiles: a device counter, read when this is called).  The
+ * rule, stated once: a batch is wide when some block fell back for 3 or more
+ * of its 8 tiles, and a wide batch sends the next 64 column batches to the
+ * block-per-tile join.  Batches whose locate was the general instance always
+ * take it.  Both joins give the same verdicts. */
+typedef struct hsc_join_stats_t {
+    uint64_t wave_batches, block_batches;
+    uint64_t wave_fallback_tiles;
+} hsc_join_stats_t;
+int hsc_join_stats(hsc_ctx *ctx, hsc_join_stats_t *out);
 
 int hsc_collector_create(hsc_ctx *ctx, int max_batch, int max_wait_us, hsc_collector **out);
 void hsc_collector_destroy(hsc_collector *col);

@@ -9,7 +9,10 @@ the recent lists rarely answer.
 
 Per snap_recent one line: us per batch on one stream and on two (the median of
 `regions` timed regions of `steps` probes over a ring of `batches` batches),
-the conflict rate, join records per batch and full_tile_joins per batch.
+the conflict rate, join records per batch and full_tile_joins per batch, and
+(a library that has hsc_join_stats) the column batches each join kernel took
+and the tiles the wave-per-tile join left to a whole block, over all of the
+setting's probes.
 HSC_LIB picks the library, as everywhere.
 """
 import argparse
@@ -52,7 +55,9 @@ def main():
     streams = [torch.cuda.current_stream(), torch.cuda.Stream(device=dev)]
     T = args.n_txn
     verdicts = [torch.zeros(T, dtype=torch.uint8, device=dev) for _ in streams]
+    has_join_stats = hasattr(v.lib, "hsc_join_stats")
     for sr in args.snap_recent:
+        j0 = v.join_stats() if has_join_stats else None
         batches = []
         for bi in range(args.batches):
             rs = config2(seed=SEED_CONFIG2 + 7919 * bi, n_commits=args.n_commits, n_txn=T,
@@ -89,6 +94,9 @@ def main():
         print(f"snap_recent {sr}: one stream {out[1]:.2f} us/batch, two streams {out[2]:.2f} us/batch, "
               f"conflicts {np.mean(conf):.3f}, join records per batch {int(np.mean(recs))}, "
               f"full_tile_joins per batch {full:.0f}", flush=True)
+        if has_join_stats:
+            j1 = v.join_stats()
+            print("    " + ", ".join(f"{k} +{j1[k] - j0[k]}" for k in j1), flush=True)
     v.close()
 
 

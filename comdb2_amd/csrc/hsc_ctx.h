@@ -726,6 +726,8 @@ struct hsc_ctx {
     ListOut lists_out;
     InternalBufs internal;   // hsc_dep_graph_internal / _internal_lists: device scratch, host results
     InternalOut internal_out;
+    LinearBufs linear;       // hsc_linear_check: the device arena, host results
+    LinearOut linear_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

@@ -909,6 +909,45 @@ struct InternalOut {  // host results (hsc_internal_report points into them)
 hipError_t graph_internal(const InternalIn &in, ResolveBufs &r, InternalBufs &b, bool arrays, InternalOut &out,
                           hipStream_t s);
 hipError_t warm_internal();
+// Linearizability search (hsc_linear.hip): one workgroup per
+// key runs the key's event program -- calls and returns in history order, the
+// values as dense per-key ids (0 = nil) -- over a set of configurations in LDS.
+constexpr uint32_t kLinSlots = 32;      // ops pending at once on a key (HSC_LIN_SLOTS)
+constexpr uint32_t kLinCap = 4096;      // configurations alive inside one step (HSC_LIN_CAP)
+constexpr uint32_t kLinTable = 8192;    // slots of the largest hash set (load <= 1/2)
+constexpr uint32_t kLinMinTable = 256;  // and of the smallest
+constexpr int kLinThreads = 512;
+constexpr uint32_t kLinEvBuf = 256;     // events of the program staged in LDS at a time
+struct alignas(16) LinEvent {  // w: bit 0 = return, bits 1-5 the slot, bits 8-9 f of a call; a, b: value ids
+    uint32_t w, a, b;
+    uint32_t op;  // the history's op (the host's, for the report)
+};
+struct LinKey {  // one launched key
+    uint32_t ev_off, nev;  // its events in the program
+    uint32_t init;         // initial state id
+    uint32_t seen_off;     // its flags in `seen` (one per value id)
+};
+struct LinResult {  // what the key's workgroup writes
+    uint32_t verdict, cause;
+    uint32_t fail_ev;      // BAD: the key's event (a return) that left no configuration
+    uint32_t peak, final_n;
+    uint32_t expanded_lo, expanded_hi;
+    uint32_t pad;
+};
+struct LinearBufs {
+    DBuf arena;  // events | keys | results | seen, one upload
+    void release_all() { arena.release(); }
+};
+struct LinearOut {  // host results (hsc_lin_report points into them)
+    std::vector<uint8_t> verdict, cause;
+    std::vector<uint32_t> fail_op, prev_ok, peak, final_n;
+    std::vector<uint64_t> state_off;
+    std::vector<int64_t> state_val;
+};
+// seen[key.seen_off + id] := 1 for the states of a BAD key's last set (zeroed by the caller)
+hipError_t linear_search(const LinEvent *prog, const LinKey *keys, uint32_t nkeys, LinResult *res, uint8_t *seen,
+                         hipStream_t s);
+hipError_t warm_linear();
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {

@@ -207,6 +207,28 @@ INTERNAL_COUNTERS = ("nops", "ntxn", "checked_reads", "bad_reads", "compared_ele
                      "sort_packed")
 
 
+class _LinOps(C.Structure):
+    """hsc_lin_ops."""
+    _fields_ = [("nops", C.c_size_t), ("nkeys", C.c_uint32), ("key", _p), ("f", _p), ("a", _p), ("b", _p),
+                ("invoke", _p), ("complete", _p), ("init", _p)]
+
+
+class LinReport(C.Structure):
+    """hsc_lin_report: the arrays are host memory of the context."""
+    _fields_ = [("nkeys", C.c_uint32), ("verdict", _p), ("cause", _p), ("fail_op", _p), ("prev_ok", _p),
+                ("peak_configs", _p), ("final_configs", _p), ("state_off", _p), ("state_val", _p),
+                ("bad", C.c_uint32), ("unknown", C.c_uint32), ("events", C.c_uint64), ("expanded", C.c_uint64),
+                ("dropped_open_reads", C.c_uint64), ("ms", C.c_float)]
+
+
+# hsc_linear_check (include/hip_serial.h)
+LIN_READ, LIN_WRITE, LIN_CAS = 0, 1, 2
+LIN_NIL = -(1 << 63)
+LIN_SLOTS, LIN_CAP = 32, 4096
+LIN_BAD, LIN_OK, LIN_UNKNOWN = 0, 1, 2
+LIN_CAUSE_SLOTS, LIN_CAUSE_CONFIGS = 1, 2
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -286,7 +308,7 @@ EXPORTS = [
     "hsc_dep_graph_anomalies", "hsc_dep_graph_si",
     "hsc_dep_graph_resolve", "hsc_dep_graph_build_resolved", "hsc_dep_graph_resolve_sort_path",
     "hsc_dep_graph_resolve_lists", "hsc_dep_graph_build_lists",
-    "hsc_dep_graph_internal", "hsc_dep_graph_internal_lists",
+    "hsc_dep_graph_internal", "hsc_dep_graph_internal_lists", "hsc_linear_check",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -383,6 +405,7 @@ def load() -> C.CDLL:
         "hsc_dep_graph_build_lists": (C.c_int, [_p, C.c_int, C.POINTER(GraphStats)]),
         "hsc_dep_graph_internal": (C.c_int, [_p, C.c_uint, C.POINTER(InternalReport)]),
         "hsc_dep_graph_internal_lists": (C.c_int, [_p, C.c_uint, C.POINTER(InternalReport)]),
+        "hsc_linear_check": (C.c_int, [_p, C.POINTER(_LinOps), C.POINTER(LinReport)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
         "hsc_window_ingest_raw": (C.c_int, [_p, C.POINTER(_RawLog)]),
@@ -1375,6 +1398,46 @@ class Validator:
         read of an OK txn against its txn's previous read of the key and the
         txn's own appends since.  As graph_internal otherwise."""
         return self._internal(self.lib.hsc_dep_graph_internal_lists, "hsc_dep_graph_internal_lists", arrays)
+
+    def linear_check(self, ops, init=None) -> dict:
+        """Linearizability of a compare-and-set register history, a search per
+        key on the GPU (hsc_linear_check; knossos' checker/linearizable over
+        cas-register-comdb2).  ``ops``: a mapping with ``nkeys`` and the per-op
+        arrays ``key``, ``f`` (LIN_READ / LIN_WRITE / LIN_CAS), ``a``, ``b``
+        (LIN_NIL: nil), ``invoke``, ``complete`` (RT_OPEN: never completed) of
+        the ops that may have taken effect; ``init``: the registers' initial
+        values per key (None: all nil).  Returns copies of the report:
+        per key ``verdict`` (LIN_BAD / LIN_OK / LIN_UNKNOWN), ``cause``,
+        ``fail_op``, ``prev_ok``, ``peak_configs``, ``final_configs`` and
+        ``possible_values`` (a list per key: for a BAD key the register values
+        the search held before the failing op, LIN_NIL among them as None),
+        and the totals ``bad``, ``unknown``, ``events``, ``expanded``,
+        ``dropped_open_reads``, ``ms``."""
+        nkeys = int(ops["nkeys"])
+        cols = {k: np.ascontiguousarray(ops[k], dt) for k, dt in
+                (("key", np.uint32), ("f", np.uint8), ("a", np.int64), ("b", np.int64),
+                 ("invoke", np.uint64), ("complete", np.uint64))}
+        n = len(cols["key"])
+        if any(v.ndim != 1 or len(v) != n for v in cols.values()):
+            raise ValueError("the op arrays must be 1-d and of one length")
+        s = _LinOps(nops=n, nkeys=nkeys, **{k: v.ctypes.data for k, v in cols.items()})
+        if init is not None:
+            iv = np.ascontiguousarray(init, np.int64)
+            if iv.shape != (nkeys,):
+                raise ValueError("init must hold one value per key")
+            s.init = iv.ctypes.data
+        a = LinReport()
+        self._chk(self.lib.hsc_linear_check(self.ctx, C.byref(s), C.byref(a)), "hsc_linear_check")
+        arr = _copy_out
+        out = {k: getattr(a, k) for k in ("nkeys", "bad", "unknown", "events", "expanded", "dropped_open_reads", "ms")}
+        for k, dt in (("verdict", np.uint8), ("cause", np.uint8), ("fail_op", np.uint32), ("prev_ok", np.uint32),
+                      ("peak_configs", np.uint32), ("final_configs", np.uint32)):
+            out[k] = arr(getattr(a, k), nkeys, dt)
+        off = arr(a.state_off, nkeys + 1, np.uint64)
+        vals = arr(a.state_val, int(off[-1]), np.int64)
+        out["possible_values"] = [[None if v == LIN_NIL else int(v) for v in vals[int(off[k]):int(off[k + 1])]]
+                                  for k in range(nkeys)]
+        return out
 
     def probe_device(self, batch: ProbeBatch) -> None:
         self._chk(self.lib.hsc_probe_device(self.ctx, C.byref(batch)), "hsc_probe_device")

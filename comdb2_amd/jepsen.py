@@ -76,6 +76,14 @@ history does not carry.  A list-append history needs no such premise:
 its longest read (``Validator.graph_resolve_lists``), report G1a / G1b,
 incompatible orders and duplicated elements, and run the same analyses on the
 edges that order gives.
+
+A register history without ``:uid`` (the reference's Clojure register
+workload: ``rand-int 5`` values) gives value matching nothing to tell two
+writers of one value apart, so the register conversion above is a guess there.
+:func:`check_linear_edn` judges such a history the way the reference does, by
+knossos' linearizability search over the cas-register model
+(``Validator.linear_check``: a search per key on the GPU, no graph), and
+:func:`cas_register_history_edn` generates histories of that form.
 """
 from __future__ import annotations
 
@@ -960,6 +968,154 @@ def check_dirty_reads_edn(validator, text: str, n: Optional[int] = None) -> dict
 
 
 # ---------------------------------------------------------------------------
+# linearizability of register histories: a search, not a graph
+# ---------------------------------------------------------------------------
+LIN_READ, LIN_WRITE, LIN_CAS = 0, 1, 2   # hsc_linear_check's f
+LIN_NIL = -(1 << 63)                     # HSC_LIN_NIL
+LIN_BAD, LIN_OK, LIN_UNKNOWN = 0, 1, 2   # its verdicts
+LIN_CAUSES = {0: None, 1: "slots", 2: "configs"}
+_LIN_F = {":read": LIN_READ, ":write": LIN_WRITE, ":cas": LIN_CAS}
+
+
+@dataclasses.dataclass
+class LinOps:
+    """A register history as hsc_linear_check takes it: the ops that may have
+    taken effect (``:ok``, and ``:info`` / unpaired as open ops)."""
+    nkeys: int
+    key: np.ndarray
+    f: np.ndarray
+    a: np.ndarray
+    b: np.ndarray
+    invoke: np.ndarray
+    complete: np.ndarray
+    keys: List[object]        # key index -> the history's key (None: the single register)
+    completions: List[dict]   # per op: its completion as parsed (an unpaired op: its invoke)
+    ok: int = 0
+    failed: int = 0           # :fail completions (dropped with their invokes)
+    info: int = 0
+    unpaired: int = 0
+    orphans: int = 0          # completions without an invoke (ignored)
+    use_time: bool = False    # positions are ``:time`` (else line indices)
+
+    def arrays(self) -> dict:
+        """What ``Validator.linear_check`` takes."""
+        return {k: getattr(self, k) for k in ("nkeys", "key", "f", "a", "b", "invoke", "complete")}
+
+
+def lin_ops_from_register_edn(text: str, independent: bool = False) -> LinOps:
+    """A knossos register history (``:f :read / :write / :cas``, no ``:uid``
+    needed) -> :class:`LinOps`, by knossos' history completion
+    (linearizable/jepsen/src/knossos/history.clj:87-171): invokes pair with
+    their completions by ``:process``; an op that completes ``:fail`` never
+    happened and is dropped, invoke included; an ``:ok`` op takes its value
+    from the completion; an ``:info`` or unpaired op stays open with its
+    invoke's value.  Keys: ``:key`` where an op carries one, the ``k`` of
+    ``[k v]`` / ``[k [cur new]]`` values with ``independent`` (the reference's
+    independent/tuple), else one register.  Positions are ``:time`` when every
+    kept invoke and completion carries an integer one and every closed op's
+    completion is later than its invoke, else line indices."""
+    rows = []  # (invoke, completion or None, invoke line, completion line)
+    pending: Dict[object, Tuple[dict, int]] = {}
+    failed = orphans = 0
+    for i, op in enumerate(_flatten(parse_edn(text))):
+        if not isinstance(op, dict):
+            continue
+        t, p = op.get(":type"), op.get(":process")
+        if t == ":invoke":
+            if p in pending:
+                rows.append(pending[p] + (None, -1))
+            pending[p] = (op, i)
+        elif t in (":ok", ":fail", ":info"):
+            if p not in pending:
+                orphans += 1
+                continue
+            inv, il = pending.pop(p)
+            if t == ":fail":
+                failed += 1
+            else:
+                rows.append((inv, il, op, i))
+    rows += [v + (None, -1) for v in pending.values()]
+    rows.sort(key=lambda r: r[1])
+    closed = [r for r in rows if r[2] is not None and r[2].get(":type") == ":ok"]
+    stamped = [o for inv, _, op, _ in rows for o in ((inv, op) if op is not None else (inv,))]
+    use_time = (all(type(o.get(":time")) is int for o in stamped)
+                and all(inv[":time"] < op[":time"] for inv, _, op, _ in closed))
+    key_ix: Dict[object, int] = {}
+    key, f, a, b, invoke, complete, comps = [], [], [], [], [], [], []
+    n_ok = n_info = n_open = 0
+    for inv, il, op, ol in rows:
+        is_ok = op is not None and op.get(":type") == ":ok"
+        fk = inv.get(":f")
+        if fk not in _LIN_F:
+            raise ValueError(f"not a register op: {fk!r}")
+        val = op.get(":value", inv.get(":value")) if is_ok else inv.get(":value")
+        k = inv.get(":key")
+        if independent:
+            k, val = val
+        if fk == ":cas":
+            cur, new = val
+        else:
+            cur, new = val, None
+        key.append(key_ix.setdefault(k, len(key_ix)))
+        f.append(_LIN_F[fk])
+        a.append(LIN_NIL if cur is None else int(cur))
+        b.append(LIN_NIL if new is None else int(new))
+        invoke.append(inv[":time"] if use_time else il)
+        complete.append(None if not is_ok else op[":time"] if use_time else ol)
+        comps.append(op if op is not None else inv)
+        n_ok += is_ok
+        n_info += op is not None and not is_ok
+        n_open += op is None
+    base = min([0] + invoke)  # (a clock that starts below zero)
+    return LinOps(len(key_ix), np.array(key, np.uint32), np.array(f, np.uint8), np.array(a, np.int64),
+                  np.array(b, np.int64), np.array([t - base for t in invoke], np.uint64),
+                  np.array([RT_OPEN if t is None else t - base for t in complete], np.uint64),
+                  list(key_ix), comps, n_ok, failed, n_info, n_open, orphans, use_time)
+
+
+def linear_report(ops: LinOps, res: dict) -> dict:
+    """``Validator.linear_check``'s dict in the history's terms: ``valid``
+    (True; False if a key is not linearizable; else "unknown" if a key's search
+    passed a limit), ``keys`` -- per history key its ``verdict`` (True / False /
+    "unknown"), ``cause`` ("slots" / "configs" for unknown), ``op`` (the
+    completion whose return left no configuration), ``previous_ok`` (the key's
+    last completion before it) and ``possible_values`` (what the register could
+    hold before it; None = nil), ``peak_configs``, ``final_configs`` -- and the
+    counts and ``ms``."""
+    names = {LIN_BAD: False, LIN_OK: True, LIN_UNKNOWN: "unknown"}
+    keys = {}
+    for k, name in enumerate(ops.keys):
+        bad = res["verdict"][k] == LIN_BAD
+        fo, po = int(res["fail_op"][k]), int(res["prev_ok"][k])
+        keys[name] = {"verdict": names[int(res["verdict"][k])], "cause": LIN_CAUSES[int(res["cause"][k])],
+                      "op": ops.completions[fo] if bad else None,
+                      "previous_ok": ops.completions[po] if bad and po != 0xFFFFFFFF else None,
+                      "possible_values": res["possible_values"][k] if bad else None,
+                      "peak_configs": int(res["peak_configs"][k]), "final_configs": int(res["final_configs"][k])}
+    report = {"valid": False if res["bad"] else "unknown" if res["unknown"] else True, "keys": keys,
+              "ok": ops.ok, "failed": ops.failed, "info": ops.info, "unpaired": ops.unpaired}
+    report.update({k: res[k] for k in ("bad", "unknown", "events", "expanded", "dropped_open_reads", "ms")})
+    return report
+
+
+def check_linear_edn(validator, text: str, init=None, independent: bool = False) -> dict:
+    """knossos' checker/linearizable over cas-register-comdb2 through the GPU:
+    :func:`lin_ops_from_register_edn`, ``Validator.linear_check``,
+    :func:`linear_report` (plus ``history``, the :class:`LinOps`).  ``init``:
+    the registers' initial value (None: nil), or a dict from history key to
+    it."""
+    ops = lin_ops_from_register_edn(text, independent)
+    if init is None:
+        iv = None
+    else:
+        per = init if isinstance(init, dict) else {k: init for k in ops.keys}
+        iv = np.array([LIN_NIL if per.get(k) is None else int(per[k]) for k in ops.keys], np.int64)
+    report = linear_report(ops, validator.linear_check(ops.arrays(), iv))
+    report["history"] = ops
+    return report
+
+
+# ---------------------------------------------------------------------------
 # generated histories (test inputs; the reference's clients need a live
 # cluster and a JVM)
 # ---------------------------------------------------------------------------
@@ -1275,3 +1431,89 @@ def dirty_reads_edn(seed: int, n_ops: int = 600, n_rows: int = 4, fail: float = 
             lines.append(f"{{:type :invoke :f :read :value nil :process {p} :time {t}}}")
             lines.append(f"{{:type :ok :f :read :value [{' '.join(map(str, vals))}] :process {p} :time {t + 5}}}")
     return "\n".join(lines) + "\n", injected
+
+
+def cas_register_history_edn(seed: int, n_ops: int = 1000, n_procs: int = 5, n_keys: int = 1, n_values: int = 5,
+                             fail: float = 0.05, info: float = 0.02, stale: float = 0.0,
+                             max_open: Optional[int] = None, independent: bool = False) -> Tuple[str, dict]:
+    """A knossos-form history of the reference's register workload (core.clj:
+    567-613: read / write / cas of ``rand-int n_values`` values, no ``:uid``)
+    over one linearizable register per key, with overlapping ops: every op is
+    invoked, takes effect at some later line and completes at a later one
+    still, while other processes do the same.  ``fail`` of the ops complete
+    ``:fail`` without an effect, as does a cas whose ``cur`` is not the
+    register's value when it takes effect.  ``info`` of the writes and cas
+    complete ``:info`` -- about half of them took effect -- and their process
+    retires (its next op runs as process + n_procs, as Jepsen does); at most
+    ``max_open`` of them per key when given.  With probability ``stale`` a read
+    returns a value the register held before an overwrite that was already
+    acknowledged when the read was invoked -- not linearizable unless an
+    overlapping or open op may have written it back.  ``n_keys`` > 1: ``:key k``, or ``[k v]``
+    values with ``independent``.  Returns (EDN text, {"stale": the completion
+    lines of the injected reads, "info": ..., "info_effective": ...})."""
+    rng = np.random.default_rng(seed)
+    state: Dict[int, Optional[int]] = {k: None for k in range(n_keys)}
+    acked: Dict[int, List[Optional[int]]] = {k: [] for k in range(n_keys)}  # values overwritten, the overwrite acknowledged
+    opened = {k: 0 for k in range(n_keys)}
+    procs = list(range(n_procs))
+    busy: Dict[int, dict] = {}
+    lines: List[str] = []
+    inj = {"stale": [], "info": 0, "info_effective": 0}
+
+    def fmt(k, v):
+        body = "nil" if v is None else f"[{v[0]} {v[1]}]" if isinstance(v, tuple) else str(v)
+        return (f":value [{k} {body}]" if independent else f":value {body}") + \
+            (f" :key {k}" if n_keys > 1 and not independent else "")
+
+    started = 0
+    while started < n_ops or busy:
+        idle = [i for i in range(n_procs) if i not in busy]
+        if started < n_ops and idle and (not busy or rng.random() < 0.5):
+            i = idle[int(rng.integers(0, len(idle)))]
+            k = int(rng.integers(0, n_keys))
+            f = (":read", ":write", ":cas")[int(rng.integers(0, 3))]
+            v = None if f == ":read" else int(rng.integers(0, n_values))
+            if f == ":cas":
+                v = (int(rng.integers(0, n_values)), v)
+            o = {"k": k, "f": f, "v": v, "phase": 0, "fate": ":ok", "old": list(acked[k])}
+            r = rng.random()
+            if r < fail:
+                o["fate"] = ":fail"
+            elif f != ":read" and r < fail + info and (max_open is None or opened[k] < max_open):
+                o["fate"] = ":info"
+                opened[k] += 1
+            busy[i] = o
+            started += 1
+            lines.append(f"{{:type :invoke :f {f} {fmt(k, v)} :process {procs[i]} :time {len(lines)}}}")
+            continue
+        i = list(busy)[int(rng.integers(0, len(busy)))]
+        o = busy[i]
+        k, f, v = o["k"], o["f"], o["v"]
+        if o["phase"] == 0:  # takes effect
+            o["phase"] = 1
+            if o["fate"] == ":fail" or (o["fate"] == ":info" and rng.random() < 0.5):
+                continue
+            if f == ":read":
+                o["v"] = state[k]
+                older = [x for x in o["old"] if x is not None and x != state[k]]  # (a nil read is a wildcard)
+                if older and rng.random() < stale:
+                    o["v"] = older[int(rng.integers(0, len(older)))]
+                    o["stale"] = True
+            elif f == ":write" or state[k] == v[0]:
+                o["prev"], o["applied"] = state[k], True
+                state[k] = v if f == ":write" else v[1]
+            else:
+                o["fate"] = ":fail" if o["fate"] == ":ok" else o["fate"]
+            continue
+        del busy[i]
+        if o.get("stale"):
+            inj["stale"].append(len(lines))
+        if o["fate"] == ":info":
+            inj["info"] += 1
+            inj["info_effective"] += bool(o.get("applied"))
+        elif o.get("applied"):
+            acked[k].append(o["prev"])
+        lines.append(f"{{:type {o['fate']} :f {f} {fmt(k, o['v'])} :process {procs[i]} :time {len(lines)}}}")
+        if o["fate"] == ":info":
+            procs[i] += n_procs
+    return "\n".join(lines) + "\n", inj

@@ -1213,6 +1213,75 @@ typedef struct hsc_internal_report {
 } hsc_internal_report;
 int hsc_dep_graph_internal(hsc_ctx *ctx, unsigned flags, hsc_internal_report *out);
 int hsc_dep_graph_internal_lists(hsc_ctx *ctx, unsigned flags, hsc_internal_report *out);
+
+/* ---- linearizability of compare-and-set register histories -----------------
+ * knossos' checker/linearizable over model/cas-register-comdb2, the checker of
+ * the reference's register-tester, its nemesis variant, the filetest and (per
+ * key, through independent/checker) the dirty-reads test
+ * (linearizable/jepsen/src/comdb2/core.clj:564-613): a search over
+ * linearizations, not a dependency graph.  DESIGN.md §5j.
+ * ops: the ops that may have taken effect (the caller leaves :fail ops out),
+ * each on one key; [invoke, complete] are history positions, complete ==
+ * HSC_RT_OPEN: the op never completed (:info or unpaired) and may take effect
+ * at any later point or never.  Equal positions overlap (calls are ordered
+ * before returns).
+ * Model (knossos/model.clj:67-93): the state is the register's value, init[key]
+ * (NULL: every key starts HSC_LIN_NIL).  write a: state := a.  cas [a b]: legal
+ * iff state == a, then state := b.  read a: legal iff a == HSC_LIN_NIL or
+ * a == state (the reference's nil-read wildcard).
+ * Search (knossos/linear.clj:66-129, 218-271): a configuration is (state, the
+ * pending ops already linearized); the completion of op i keeps the
+ * configurations that hold i and closes the others under linearizing pending
+ * ops other than i, then i.  The first completion that leaves no configuration
+ * is the key's failing op.
+ * Each key is searched by one workgroup in one launch.  Its limits are
+ * HSC_LIN_SLOTS ops pending at once on the key (open ops stay pending; open
+ * reads are dropped first: they change nothing and nothing waits for them) and
+ * HSC_LIN_CAP configurations alive inside one completion step; past either the
+ * key's verdict is HSC_LIN_UNKNOWN with the cause, as knossos answers :unknown
+ * when it runs out of memory -- never an error, never a wrong verdict, and the
+ * other keys of the call are judged.
+ * HSC_EINVAL: a NULL argument, key[i] >= nkeys, an unknown f, or invoke >=
+ * complete on a closed op.  HSC_EDEVICE: a host-only context.  nops == 0 or
+ * nkeys == 0 succeed.  The report's arrays are host memory owned by the
+ * context, never NULL, valid until the next hsc_linear_check on it. */
+#define HSC_LIN_READ  0
+#define HSC_LIN_WRITE 1
+#define HSC_LIN_CAS   2
+#define HSC_LIN_NIL   INT64_MIN
+#define HSC_LIN_SLOTS 32
+#define HSC_LIN_CAP   4096
+#define HSC_LIN_BAD     0   /* verdict */
+#define HSC_LIN_OK      1
+#define HSC_LIN_UNKNOWN 2
+#define HSC_LIN_CAUSE_SLOTS   1   /* cause of an UNKNOWN key */
+#define HSC_LIN_CAUSE_CONFIGS 2
+typedef struct hsc_lin_ops {
+    size_t nops;  uint32_t nkeys;
+    const uint32_t *key;       /* [nops] 0 .. nkeys-1 */
+    const uint8_t  *f;         /* [nops] HSC_LIN_READ / _WRITE / _CAS */
+    const int64_t  *a, *b;     /* [nops] read: a = value; write: a = value; cas: a = cur, b = new */
+    const uint64_t *invoke;    /* [nops] */
+    const uint64_t *complete;  /* [nops] HSC_RT_OPEN: never completed */
+    const int64_t  *init;      /* [nkeys] or NULL */
+} hsc_lin_ops;
+typedef struct hsc_lin_report {
+    uint32_t nkeys;
+    const uint8_t  *verdict;        /* [nkeys] */
+    const uint8_t  *cause;          /* [nkeys] 0 unless UNKNOWN */
+    const uint32_t *fail_op;        /* [nkeys] BAD: the op whose completion left no configuration; else ~0u */
+    const uint32_t *prev_ok;        /* [nkeys] BAD: the key's last op completed before it (~0u: none); else ~0u */
+    const uint32_t *peak_configs;   /* [nkeys] most configurations alive inside one step (UNKNOWN: of the steps done) */
+    const uint32_t *final_configs;  /* [nkeys] the set at the end (BAD / UNKNOWN: as it stood before the op) */
+    const uint64_t *state_off;      /* [nkeys + 1] */
+    const int64_t  *state_val;      /* BAD keys: the distinct register values of the set before the failing op, ascending */
+    uint32_t bad, unknown;          /* keys */
+    uint64_t events;                /* calls and returns in the event programs launched */
+    uint64_t expanded;              /* configurations expanded, over the completed steps */
+    uint64_t dropped_open_reads;
+    float ms;                       /* device time of the whole call */
+} hsc_lin_report;
+int hsc_linear_check(hsc_ctx *ctx, const hsc_lin_ops *ops, hsc_lin_report *out);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst

@@ -728,6 +728,10 @@ struct hsc_ctx {
     InternalOut internal_out;
     LinearBufs linear;       // hsc_linear_check: the device arena, host results
     LinearOut linear_out;
+    TallyBufs tally;         // hsc_tally_check: device scratch and sort rows of its own, host results
+    TallyOut tally_out;
+    BankBufs bank;           // hsc_bank_check: device scratch, host results
+    BankOut bank_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

@@ -948,6 +948,58 @@ struct LinearOut {  // host results (hsc_lin_report points into them)
 hipError_t linear_search(const LinEvent *prog, const LinKey *keys, uint32_t nkeys, LinResult *res, uint8_t *seen,
                          hipStream_t s);
 hipError_t warm_linear();
+// The accounting checkers (hsc_tally.hip).  Tally: three value
+// arrays -> per class the counts and the runs of consecutive values.  The
+// (value, source) sort goes through t, a set of sort rows of its own
+// (sort_rows2), as ListBufs holds one: nothing a resolve or a build left on the
+// context is touched.
+struct TallyBufs {
+    ResolveBufs t;                  // the sort's rows and scratch
+    DBuf in, rows, pay;             // the uploaded values, the (value, source) rows, their payload
+    DBuf f0, f1, spos, vsub;        // head flags / scans, sub-run positions, each value's first sub-run
+    DBuf val, cnt, rf;              // per distinct value: the value, A / K / S; the classes' run head flags
+    DBuf ct, lo, hi, mult;          // counters, the listed runs
+    void release_all();
+};
+struct TallyIn {  // host pointers
+    size_t n_attempt, n_ack, n_seen;
+    const int64_t *attempt, *ack, *seen;
+    bool multiset;
+};
+struct TallyOut {  // host results (hsc_tally_report points into them)
+    uint64_t total[3], distinct;
+    uint64_t count[HSC_TALLY_NCLASS], ndistinct[HSC_TALLY_NCLASS], runs[HSC_TALLY_NCLASS];
+    uint32_t n_listed[HSC_TALLY_NCLASS];
+    std::vector<int64_t> lo[HSC_TALLY_NCLASS], hi[HSC_TALLY_NCLASS];  // never empty
+    std::vector<uint32_t> mult[HSC_TALLY_NCLASS];
+    int sort_packed;
+};
+hipError_t tally_run(const TallyIn &in, TallyBufs &b, TallyOut &out, hipStream_t s);
+hipError_t warm_tally();
+// Bank: reads in CSR form -> per read its kind, found and negatives, the bad
+// reads listed.  off was checked by the caller (ascending from 0).
+struct BankBufs {
+    DBuf off, bal, kind, found, neg, flag, scratch, ct, listed;
+    void release_all();
+};
+struct BankIn {  // host pointers
+    size_t n_reads;
+    const uint64_t *off;
+    const int64_t *balance;
+    uint64_t n;
+    int64_t total;
+};
+struct BankOut {  // host results (hsc_bank_report points into them)
+    std::vector<uint8_t> kind;  // never empty
+    std::vector<int64_t> found;
+    std::vector<uint32_t> neg;
+    std::vector<uint64_t> listed;
+    uint64_t bad, wrong_n, wrong_total, with_negative;
+    uint32_t n_listed;
+    int group;  // lanes per read
+};
+int bank_group(uint64_t n);  // the lanes a read of the model's n gets: a power of two, at most 64
+hipError_t bank_run(const BankIn &in, BankBufs &b, BankOut &out, hipStream_t s);
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {

@@ -229,6 +229,44 @@ LIN_BAD, LIN_OK, LIN_UNKNOWN = 0, 1, 2
 LIN_CAUSE_SLOTS, LIN_CAUSE_CONFIGS = 1, 2
 
 
+# hsc_tally_check / hsc_bank_check (include/hip_serial.h)
+TALLY_MULTISET = 1
+TALLY_LIST_CAP = BANK_LIST_CAP = 4096
+TALLY_CLASSES = ("ok", "unexpected", "duplicated", "lost", "recovered")  # HSC_TALLY_OK ..
+BANK_FINE, BANK_WRONG_N, BANK_WRONG_TOTAL = 0, 1, 2
+
+
+class _TallyIn(C.Structure):
+    """hsc_tally_in."""
+    _fields_ = [("n_attempt", C.c_size_t), ("n_ack", C.c_size_t), ("n_seen", C.c_size_t),
+                ("attempt", _p), ("ack", _p), ("seen", _p)]
+
+
+class TallyClass(C.Structure):
+    """hsc_tally_class: the arrays are host memory of the context."""
+    _fields_ = [("count", C.c_uint64), ("distinct", C.c_uint64), ("runs", C.c_uint64), ("n_listed", C.c_uint32),
+                ("lo", _p), ("hi", _p), ("mult", _p)]
+
+
+class TallyReport(C.Structure):
+    """hsc_tally_report."""
+    _fields_ = [("attempts", C.c_uint64), ("acks", C.c_uint64), ("seen", C.c_uint64), ("distinct", C.c_uint64),
+                ("valid", C.c_int), ("cls", TallyClass * len(TALLY_CLASSES)), ("sort_packed", C.c_int),
+                ("ms", C.c_float)]
+
+
+class _BankIn(C.Structure):
+    """hsc_bank_in."""
+    _fields_ = [("n_reads", C.c_size_t), ("off", _p), ("balance", _p), ("n", C.c_uint64), ("total", C.c_int64)]
+
+
+class BankReport(C.Structure):
+    """hsc_bank_report: the arrays are host memory of the context."""
+    _fields_ = [("n_reads", C.c_uint64), ("bad", C.c_uint64), ("wrong_n", C.c_uint64), ("wrong_total", C.c_uint64),
+                ("reads_with_negative", C.c_uint64), ("valid", C.c_int), ("kind", _p), ("found", _p),
+                ("negatives", _p), ("n_listed", C.c_uint32), ("listed_read", _p), ("ms", C.c_float)]
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -309,6 +347,7 @@ EXPORTS = [
     "hsc_dep_graph_resolve", "hsc_dep_graph_build_resolved", "hsc_dep_graph_resolve_sort_path",
     "hsc_dep_graph_resolve_lists", "hsc_dep_graph_build_lists",
     "hsc_dep_graph_internal", "hsc_dep_graph_internal_lists", "hsc_linear_check",
+    "hsc_tally_check", "hsc_bank_check",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -406,6 +445,8 @@ def load() -> C.CDLL:
         "hsc_dep_graph_internal": (C.c_int, [_p, C.c_uint, C.POINTER(InternalReport)]),
         "hsc_dep_graph_internal_lists": (C.c_int, [_p, C.c_uint, C.POINTER(InternalReport)]),
         "hsc_linear_check": (C.c_int, [_p, C.POINTER(_LinOps), C.POINTER(LinReport)]),
+        "hsc_tally_check": (C.c_int, [_p, C.POINTER(_TallyIn), C.c_uint, C.POINTER(TallyReport)]),
+        "hsc_bank_check": (C.c_int, [_p, C.POINTER(_BankIn), C.POINTER(BankReport)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
         "hsc_window_ingest_raw": (C.c_int, [_p, C.POINTER(_RawLog)]),
@@ -1437,6 +1478,52 @@ class Validator:
         vals = arr(a.state_val, int(off[-1]), np.int64)
         out["possible_values"] = [[None if v == LIN_NIL else int(v) for v in vals[int(off[k]):int(off[k + 1])]]
                                   for k in range(nkeys)]
+        return out
+
+    def tally_check(self, attempt, ack, seen, multiset: bool = False) -> dict:
+        """The reference's checker/set -- with ``multiset`` its
+        checker/total-queue -- over three arrays of int64 values
+        (hsc_tally_check; the table in include/hip_serial.h says which ops go
+        where).  Returns copies of the report: ``attempts``, ``acks``,
+        ``seen``, ``distinct``, ``valid``, ``sort_packed``, ``ms`` and per
+        class of TALLY_CLASSES a dict of ``count``, ``distinct``, ``runs``,
+        ``n_listed`` and the listed runs as the arrays ``lo``, ``hi``,
+        ``mult``."""
+        cols = [np.ascontiguousarray(a, np.int64) for a in (attempt, ack, seen)]
+        if any(a.ndim != 1 for a in cols):
+            raise ValueError("attempt, ack and seen must be 1-d")
+        s = _TallyIn(len(cols[0]), len(cols[1]), len(cols[2]), *(a.ctypes.data for a in cols))
+        a = TallyReport()
+        self._chk(self.lib.hsc_tally_check(self.ctx, C.byref(s), TALLY_MULTISET if multiset else 0, C.byref(a)),
+                  "hsc_tally_check")
+        out = {k: getattr(a, k) for k in ("attempts", "acks", "seen", "distinct", "valid", "sort_packed", "ms")}
+        for name, q in zip(TALLY_CLASSES, a.cls):
+            out[name] = {"count": q.count, "distinct": q.distinct, "runs": q.runs, "n_listed": q.n_listed,
+                         "lo": _copy_out(q.lo, q.n_listed, np.int64), "hi": _copy_out(q.hi, q.n_listed, np.int64),
+                         "mult": _copy_out(q.mult, q.n_listed, np.uint32)}
+        return out
+
+    def bank_check(self, off, balance, n: int, total: int) -> dict:
+        """The reference's bank-checker over the :ok reads in CSR form
+        (hsc_bank_check): read i holds ``balance[off[i]:off[i + 1]]``; ``n``
+        and ``total`` are the test's model.  Returns copies of the report:
+        the counters, ``valid``, ``ms``, per read ``kind`` (BANK_FINE /
+        BANK_WRONG_N / BANK_WRONG_TOTAL), ``found`` and ``negatives``, and
+        ``listed_read``, the first BANK_LIST_CAP bad reads."""
+        off = np.ascontiguousarray(off, np.uint64)
+        bal = np.ascontiguousarray(balance, np.int64)
+        if off.ndim != 1 or bal.ndim != 1 or len(off) < 1:
+            raise ValueError("off must hold n_reads + 1 offsets, balance be 1-d")
+        nr = len(off) - 1
+        s = _BankIn(nr, off.ctypes.data, bal.ctypes.data, n, total)
+        a = BankReport()
+        self._chk(self.lib.hsc_bank_check(self.ctx, C.byref(s), C.byref(a)), "hsc_bank_check")
+        out = {k: getattr(a, k) for k in ("n_reads", "bad", "wrong_n", "wrong_total", "reads_with_negative", "valid",
+                                          "n_listed", "ms")}
+        out["kind"] = _copy_out(a.kind, nr, np.uint8)
+        out["found"] = _copy_out(a.found, nr, np.int64)
+        out["negatives"] = _copy_out(a.negatives, nr, np.uint32)
+        out["listed_read"] = _copy_out(a.listed_read, a.n_listed, np.uint64)
         return out
 
     def probe_device(self, batch: ProbeBatch) -> None:

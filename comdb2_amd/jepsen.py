@@ -84,10 +84,24 @@ writers of one value apart, so the register conversion above is a guess there.
 knossos' linearizability search over the cas-register model
 (``Validator.linear_check``: a search per key on the GPU, no graph), and
 :func:`cas_register_history_edn` generates histories of that form.
+
+The suite's other two workloads are neither graphs nor searches but
+accounting, and their checkers filter ops by ``:type`` and ``:f`` without
+pairing invokes and completions; so do the conversions here.
+:func:`check_set_edn` is ``checker/set`` (jepsen/checker.clj:108-154: attempted
+adds, acknowledged adds and the final read compared as sets; a set ``#{...}``
+parses as a list), :func:`check_total_queue_edn` is ``checker/total-queue``
+(:163-218, the same over multisets) -- both one ``Validator.tally_check`` -- and
+:func:`check_bank_edn` is the bank test's ``bank-checker`` (core.clj:152-177:
+every read's length and total against the model, ``Validator.bank_check``).
+:func:`set_report`, :func:`total_queue_report` and :func:`bank_report` are the
+pure halves; :func:`set_history_edn`, :func:`queue_history_edn` and
+:func:`bank_history_edn` generate histories with known injections.
 """
 from __future__ import annotations
 
 import dataclasses
+import fractions
 import re
 from typing import Dict, List, Optional, Tuple
 
@@ -113,8 +127,12 @@ def _tokens(text: str):
 
 
 def _parse(tokens, tok):
-    if tok in ("{", "[", "("):
-        close = {"{": "}", "[": "]", "(": ")"}[tok]
+    if tok == "#":  # a set #{...} (the set workload's final read): its elements as a list
+        if next(tokens, None) != "{":
+            raise ValueError("unsupported EDN dispatch form")
+        tok = "#{"
+    if tok in ("{", "[", "(", "#{"):
+        close = {"{": "}", "[": "]", "(": ")", "#{": "}"}[tok]
         items = []
         for t in tokens:
             if t == close:
@@ -1116,6 +1134,197 @@ def check_linear_edn(validator, text: str, init=None, independent: bool = False)
 
 
 # ---------------------------------------------------------------------------
+# the accounting checkers: set, total-queue, bank (no graph, no search)
+# ---------------------------------------------------------------------------
+TALLY_CLASSES = ("ok", "unexpected", "duplicated", "lost", "recovered")  # hsc_tally_check's classes
+
+
+def _int_value(v, what: str) -> int:
+    if type(v) is not int:
+        raise ValueError(f"{what}: not an integer value: {v!r}")
+    if not -(1 << 63) <= v < (1 << 63):
+        raise ValueError(f"{what}: a value outside 64 bits: {v!r}")
+    return v
+
+
+def _typed_ops(text: str):
+    """(type, f, op) of every op map, in history order (both layouts)."""
+    for op in _flatten(parse_edn(text)):
+        if isinstance(op, dict):
+            yield op.get(":type"), op.get(":f"), op
+
+
+@dataclasses.dataclass
+class TallyOps:
+    """The three value arrays ``Validator.tally_check`` takes.  ``seen`` is
+    None for a set history without an ``:ok :read`` (or whose last one holds
+    nil); ``read_op`` is that read's completion."""
+    attempt: np.ndarray
+    ack: np.ndarray
+    seen: Optional[np.ndarray]
+    read_op: Optional[dict] = None
+
+
+def set_ops_from_edn(text: str) -> TallyOps:
+    """checker/set's three collections (jepsen/checker.clj:114-128): the
+    values of the ``:invoke :add`` ops, of the ``:ok :add`` ops, and the
+    ``:value`` of the last ``:ok :read`` in history order.  Nothing is paired:
+    a failed add is still an attempt, a completion without its invoke still an
+    acknowledged add."""
+    attempt, ack, last = [], [], None
+    for t, f, op in _typed_ops(text):
+        if f == ":add" and t == ":invoke":
+            attempt.append(_int_value(op.get(":value"), "add"))
+        elif f == ":add" and t == ":ok":
+            ack.append(_int_value(op.get(":value"), "add"))
+        elif f == ":read" and t == ":ok":
+            last = op
+    seen = None
+    if last is not None and last.get(":value") is not None:
+        vals = last[":value"]
+        if not isinstance(vals, list):
+            raise ValueError(f"read: not a collection: {vals!r}")
+        seen = np.array([_int_value(v, "read") for v in vals], np.int64)
+    return TallyOps(np.array(attempt, np.int64), np.array(ack, np.int64), seen, last)
+
+
+def queue_ops_from_edn(text: str) -> TallyOps:
+    """checker/total-queue's three multisets (jepsen/checker.clj:169-183): the
+    values of ``:invoke :enqueue``, ``:ok :enqueue`` and ``:ok :dequeue``."""
+    cols = {(":enqueue", ":invoke"): [], (":enqueue", ":ok"): [], (":dequeue", ":ok"): []}
+    for t, f, op in _typed_ops(text):
+        if (f, t) in cols:
+            cols[(f, t)].append(_int_value(op.get(":value"), f[1:]))
+    a, k, s = (np.array(v, np.int64) for v in cols.values())
+    return TallyOps(a, k, s)
+
+
+def interval_set_str(runs) -> str:
+    """util/integer-interval-set-str (jepsen/util.clj:483-508) of the set whose
+    runs of consecutive integers are ``runs`` [(lo, hi), ...], ascending:
+    ``#{0..5 7 9..11}``."""
+    return "#{" + " ".join(str(int(lo)) if lo == hi else f"{int(lo)}..{int(hi)}" for lo, hi in runs) + "}"
+
+
+def _frac(count: int, attempts: int):
+    return fractions.Fraction(count, attempts) if attempts else fractions.Fraction(1)
+
+
+def _class_runs(res: dict, name: str) -> List[Tuple[int, int, int]]:
+    c = res[name]
+    return [(int(lo), int(hi), int(m)) for lo, hi, m in zip(c["lo"], c["hi"], c["mult"])]
+
+
+def _truncated(res: dict) -> List[str]:
+    return [c for c in TALLY_CLASSES if res[c]["runs"] > res[c]["n_listed"]]
+
+
+def set_report(ops: TallyOps, res: Optional[dict]) -> dict:
+    """checker/set's answer (jepsen/checker.clj:129-154) from a
+    ``Validator.tally_check`` dict of ``ops`` in set mode (a pure function of
+    its arguments; ``res`` is not looked at when the set was never read):
+    ``valid``; ``ok`` / ``lost`` / ``unexpected`` / ``recovered`` as the
+    reference's interval strings, built from the listed runs; ``*_count``;
+    ``*_frac`` over the attempts (1 when there are none); ``truncated`` -- the
+    classes with more runs than the entry lists, whose strings stop early;
+    ``tally`` -- the entry's dict."""
+    if ops.seen is None:
+        return {"valid": "unknown", "error": "Set was never read"}
+    report = {"valid": bool(res["valid"]), "truncated": _truncated(res), "tally": res}
+    for c in ("ok", "lost", "unexpected", "recovered"):
+        report[c] = interval_set_str((lo, hi) for lo, hi, _ in _class_runs(res, c))
+        report[c + "_count"] = int(res[c]["count"])
+        report[c + "_frac"] = _frac(int(res[c]["count"]), int(res["attempts"]))
+    return report
+
+
+def check_set_edn(validator, text: str) -> dict:
+    """checker/set through the GPU: :func:`set_ops_from_edn`,
+    ``Validator.tally_check``, :func:`set_report`.  A history without an
+    ``:ok :read`` makes no GPU call."""
+    ops = set_ops_from_edn(text)
+    if ops.seen is None:
+        return set_report(ops, None)
+    return set_report(ops, validator.tally_check(ops.attempt, ops.ack, ops.seen))
+
+
+def total_queue_report(ops: TallyOps, res: dict) -> dict:
+    """checker/total-queue's answer (jepsen/checker.clj:184-218) from a
+    ``Validator.tally_check`` dict of ``ops`` in multiset mode (a pure
+    function): ``valid`` -- no lost and no unexpected; the five classes as run
+    lists ``[(lo, hi, mult), ...]`` (mult copies of every integer lo .. hi);
+    ``*_count``, ``*_frac``, ``truncated``, ``tally``."""
+    report = {"valid": bool(res["valid"]), "truncated": _truncated(res), "tally": res}
+    for c in TALLY_CLASSES:
+        report[c] = _class_runs(res, c)
+        report[c + "_count"] = int(res[c]["count"])
+        report[c + "_frac"] = _frac(int(res[c]["count"]), int(res["attempts"]))
+    return report
+
+
+def check_total_queue_edn(validator, text: str) -> dict:
+    """checker/total-queue through the GPU: :func:`queue_ops_from_edn`,
+    ``Validator.tally_check(multiset=True)``, :func:`total_queue_report`."""
+    ops = queue_ops_from_edn(text)
+    return total_queue_report(ops, validator.tally_check(ops.attempt, ops.ack, ops.seen, multiset=True))
+
+
+@dataclasses.dataclass
+class BankOps:
+    """The ``:ok :read`` ops of a bank history in CSR form, as
+    ``Validator.bank_check`` takes them, and their completions."""
+    off: np.ndarray
+    balance: np.ndarray
+    completions: List[dict]
+
+
+def bank_ops_from_edn(text: str) -> BankOps:
+    """bank-checker's reads (core.clj:157-161): the balances of every
+    ``:ok :read`` in history order."""
+    off, bal, comps = [0], [], []
+    for t, f, op in _typed_ops(text):
+        if t != ":ok" or f != ":read":
+            continue
+        vals = op.get(":value")
+        if not isinstance(vals, list):
+            raise ValueError(f"read: not a collection of balances: {vals!r}")
+        bal.extend(_int_value(v, "read") for v in vals)
+        off.append(len(bal))
+        comps.append(op)
+    return BankOps(np.array(off, np.uint64), np.array(bal, np.int64), comps)
+
+
+_BANK_KINDS = {1: "wrong-n", 2: "wrong-total"}
+
+
+def bank_report(ops: BankOps, res: dict, n: int, total: int) -> dict:
+    """bank-checker's answer (core.clj:162-177) from a ``Validator.bank_check``
+    dict (a pure function): ``valid``; ``bad_reads`` -- for the listed bad
+    reads in history order ``{"type": "wrong-n" | "wrong-total", "expected",
+    "found", "op"}``; ``bad_read_count``, ``wrong_n``, ``wrong_total``;
+    ``negative_reads`` -- reads holding a negative balance, which the
+    reference's checker does not judge and ``valid`` does not count;
+    ``truncated`` -- more bad reads than listed; ``bank`` -- the entry's dict."""
+    bad = []
+    for i in res["listed_read"]:
+        k = int(res["kind"][int(i)])
+        bad.append({"type": _BANK_KINDS[k], "expected": n if k == 1 else total, "found": int(res["found"][int(i)]),
+                    "op": ops.completions[int(i)]})
+    return {"valid": bool(res["valid"]), "bad_reads": bad, "bad_read_count": int(res["bad"]),
+            "wrong_n": int(res["wrong_n"]), "wrong_total": int(res["wrong_total"]),
+            "negative_reads": int(res["reads_with_negative"]), "truncated": res["bad"] > res["n_listed"],
+            "bank": res}
+
+
+def check_bank_edn(validator, text: str, n: int, total: int) -> dict:
+    """bank-checker through the GPU: :func:`bank_ops_from_edn`,
+    ``Validator.bank_check``, :func:`bank_report`.  ``n`` and ``total`` are the
+    test's ``:model`` (accounts, the sum of their starting balances)."""
+    ops = bank_ops_from_edn(text)
+    return bank_report(ops, validator.bank_check(ops.off, ops.balance, n, total), n, total)
+
+
+# ---------------------------------------------------------------------------
 # generated histories (test inputs; the reference's clients need a live
 # cluster and a JVM)
 # ---------------------------------------------------------------------------
@@ -1517,3 +1726,146 @@ def cas_register_history_edn(seed: int, n_ops: int = 1000, n_procs: int = 5, n_k
         if o["fate"] == ":info":
             procs[i] += n_procs
     return "\n".join(lines) + "\n", inj
+
+
+def _interleave(rng, n_procs: int, n_items: int, invoke, complete) -> List[str]:
+    """Lines of n_items ops run by n_procs processes, one op in flight per
+    process: ``invoke(i, p)`` / ``complete(i, p)`` give an op's two lines."""
+    lines, pending, nxt = [], {}, 0
+    while nxt < n_items or pending:
+        p = int(rng.integers(0, n_procs))
+        if p in pending:
+            lines.append(complete(pending.pop(p), p))
+        elif nxt < n_items:
+            lines.append(invoke(nxt, p))
+            pending[p] = nxt
+            nxt += 1
+    return lines
+
+
+def set_history_edn(seed: int, n_adds: int = 1000, n_procs: int = 5, lose: int = 0, phantom: int = 0,
+                    info_frac: float = 0.0) -> Tuple[str, dict]:
+    """A sets-test history (core.clj:252-272): adds of 0 .. n_adds - 1 by
+    n_procs processes, each ``:ok``, ``:fail`` (3 %, not in the set) or, with
+    probability ``info_frac``, ``:info`` (in the set or not, a coin each), then
+    one final read.  ``lose`` acknowledged adds are missing from the read,
+    ``phantom`` values nobody added are in it.  Returns (EDN text, the
+    injected ``lost`` / ``unexpected`` / ``recovered`` values, sorted, and
+    ``ok``, the attempted values the read holds)."""
+    rng = np.random.default_rng(seed)
+    kind = np.where(rng.random(n_adds) < info_frac, 2, np.where(rng.random(n_adds) < 0.03, 1, 0))
+    names = (":ok", ":fail", ":info")
+    lines = _interleave(rng, n_procs, n_adds,
+                        lambda i, p: f"{{:type :invoke, :f :add, :value {i}, :process {p}}}",
+                        lambda i, p: f"{{:type {names[kind[i]]}, :f :add, :value {i}, :process {p}}}")
+    acked = np.flatnonzero(kind == 0)
+    lost = np.sort(rng.choice(acked, size=min(lose, len(acked)), replace=False)) if lose else np.zeros(0, np.int64)
+    infos = np.flatnonzero(kind == 2)
+    recovered = infos[rng.random(len(infos)) < 0.5]
+    unexpected = n_adds + 100 + 2 * np.arange(phantom)
+    final = np.sort(np.concatenate([np.setdiff1d(acked, lost), recovered, unexpected])).astype(np.int64)
+    lines.append("{:type :invoke, :f :read, :value nil, :process 0}")
+    lines.append("{:type :ok, :f :read, :value #{" + " ".join(str(int(v)) for v in final) + "}, :process 0}")
+    inj = {"lost": [int(v) for v in lost], "unexpected": [int(v) for v in unexpected],
+           "recovered": [int(v) for v in recovered], "ok": [int(v) for v in final if v < n_adds]}
+    return "\n".join(lines) + "\n", inj
+
+
+def queue_history_edn(seed: int, n_enqueues: int = 1000, n_procs: int = 5, n_values: int = 64, lose: int = 0,
+                      duplicate: int = 0, unexpected: int = 0, info_frac: float = 0.0) -> Tuple[str, dict]:
+    """A total-queue history: n_enqueues enqueues of values below n_values
+    (so values repeat), then a drain.  Values of the upper half may complete
+    ``:info`` (probability ``info_frac``; dequeued or not, a coin each); the
+    injections touch the lower half only, one value each, so that they add up
+    exactly: ``lose`` acknowledged elements never dequeued, ``duplicate``
+    extra dequeues of a value every enqueue of which was acknowledged and
+    dequeued, ``unexpected`` dequeues of values nobody enqueued.  Returns
+    (EDN text, the injected ``lost`` / ``duplicated`` / ``unexpected`` /
+    ``recovered`` multisets as sorted (value, count) lists)."""
+    rng = np.random.default_rng(seed)
+    half = max(n_values // 2, 1)
+    vals = rng.integers(0, n_values, n_enqueues)
+    info = (vals >= half) & (rng.random(n_enqueues) < info_frac)
+    lines = _interleave(rng, n_procs, n_enqueues,
+                        lambda i, p: f"{{:type :invoke, :f :enqueue, :value {vals[i]}, :process {p}}}",
+                        lambda i, p: (f"{{:type {':info' if info[i] else ':ok'}, :f :enqueue, :value {vals[i]}, "
+                                      f":process {p}}}"))
+    out = list(vals[~info])
+    low = np.unique(vals[vals < half])
+    picks = rng.permutation(low)[:min(lose + duplicate, len(low))]
+    lost, dup = {}, {}
+    for v in picks[:lose]:
+        lost[int(v)] = int(rng.integers(1, int((vals == v).sum()) + 1))
+        for _ in range(lost[int(v)]):
+            out.remove(v)
+    for v in picks[lose:]:
+        dup[int(v)] = int(rng.integers(1, 4))
+        out += [v] * dup[int(v)]
+    rec = {}
+    for v in vals[info][rng.random(int(info.sum())) < 0.5]:
+        rec[int(v)] = rec.get(int(v), 0) + 1
+        out.append(v)
+    unx = {}
+    for k in range(unexpected):
+        unx[n_values + 100 + 3 * k] = 1 + k % 2
+        out += [n_values + 100 + 3 * k] * (1 + k % 2)
+    out = [int(v) for v in rng.permutation(np.array(out, np.int64))]
+    lines += _interleave(rng, n_procs, len(out),
+                         lambda i, p: f"{{:type :invoke, :f :dequeue, :value nil, :process {p}}}",
+                         lambda i, p: f"{{:type :ok, :f :dequeue, :value {out[i]}, :process {p}}}")
+    inj = {"lost": sorted(lost.items()), "duplicated": sorted(dup.items()), "unexpected": sorted(unx.items()),
+           "recovered": sorted(rec.items())}
+    return "\n".join(lines) + "\n", inj
+
+
+def bank_history_edn(seed: int, n: int = 5, start: int = 10, n_ops: int = 500, n_procs: int = 5,
+                     skew_reads: int = 0, short_reads: int = 0) -> Tuple[str, dict]:
+    """A bank-test history (core.clj:71-150, :297-318): n accounts of
+    ``start`` each, n_ops ops, half reads and half transfers, executed in
+    order (a transfer that would go negative completes ``:fail``).
+    ``skew_reads`` reads are snapshots taken between the two updates of a
+    transfer of at least 1 -- they miss its credit; ``short_reads`` reads lack
+    their last balance.  Returns (EDN text, ``skewed``: [(read, amount)] and
+    ``short``: [read], reads numbered among the ``:ok`` reads in history
+    order)."""
+    rng = np.random.default_rng(seed)
+    bal = [start] * n
+    is_read = rng.random(n_ops) < 0.5
+    reads = np.flatnonzero(is_read)
+    marked = rng.permutation(reads)[:skew_reads + short_reads]
+    skew_at, short_at = set(marked[:skew_reads].tolist()), set(marked[skew_reads:].tolist())
+    lines, skewed, short, nread = [], [], [], 0
+    for i in range(n_ops):
+        p = int(rng.integers(0, n_procs))
+        if is_read[i]:
+            lines.append(f"{{:type :invoke, :f :read, :process {p}}}")
+            snap = list(bal)
+            if i in skew_at:  # a transfer by another process, seen half done
+                src = int(rng.choice([a for a in range(n) if bal[a] >= 1]))
+                dst = (src + 1 + int(rng.integers(0, max(n - 1, 1)))) % n
+                amount = int(rng.integers(1, min(bal[src], 4) + 1))
+                q = (p + 1) % max(n_procs, 2)
+                val = f"{{:from {src}, :to {dst}, :amount {amount}}}"
+                lines.insert(len(lines) - 1, f"{{:type :invoke, :f :transfer, :value {val}, :process {q}}}")
+                snap[src] -= amount
+                bal[src] -= amount
+                bal[dst] += amount
+                skewed.append((nread, amount))
+            elif i in short_at:
+                snap = snap[:-1]
+                short.append(nread)
+            lines.append(f"{{:type :ok, :f :read, :value [{' '.join(map(str, snap))}], :process {p}}}")
+            if i in skew_at:
+                lines.append(f"{{:type :ok, :f :transfer, :value {val}, :process {q}}}")
+            nread += 1
+            continue
+        src, dst, amount = int(rng.integers(0, n)), int(rng.integers(0, n)), int(rng.integers(0, 5))
+        val = f"{{:from {src}, :to {dst}, :amount {amount}}}"
+        lines.append(f"{{:type :invoke, :f :transfer, :value {val}, :process {p}}}")
+        if bal[src] - amount < 0:
+            lines.append(f"{{:type :fail, :f :transfer, :value [:negative {src} {bal[src] - amount}], :process {p}}}")
+        else:
+            bal[src] -= amount
+            bal[dst] += amount
+            lines.append(f"{{:type :ok, :f :transfer, :value {val}, :process {p}}}")
+    return "\n".join(lines) + "\n", {"skewed": skewed, "short": short}

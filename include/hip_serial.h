@@ -1282,6 +1282,107 @@ typedef struct hsc_lin_report {
     float ms;                       /* device time of the whole call */
 } hsc_lin_report;
 int hsc_linear_check(hsc_ctx *ctx, const hsc_lin_ops *ops, hsc_lin_report *out);
+
+/* ---- the accounting checkers: set, total-queue, bank -------------------------
+ * The other two workloads of the reference's Jepsen suite
+ * (linearizable/jepsen/src/comdb2/core.clj: set-client and sets-test :223-272,
+ * the bank client, checker and tests :71-177, :274-318).  Neither is a graph or a search: both count.  DESIGN.md §5k.
+ * hsc_tally_check is checker/set (jepsen/checker.clj:108-154) and, with
+ * HSC_TALLY_MULTISET, checker/total-queue (:163-218).  Like the reference it
+ * filters by :type and :f only and never pairs an invoke with its completion;
+ * the caller hands over three arrays of values, in any order:
+ *               set                         total-queue
+ *   attempt     :invoke :add                :invoke :enqueue
+ *   ack         :ok :add                    :ok :enqueue
+ *   seen        the last :ok :read's set    :ok :dequeue
+ * For a value let A, K, S be its occurrences in attempt, ack and seen, each
+ * clamped to 1 without HSC_TALLY_MULTISET (a set holds a value once).  Its
+ * multiplicity in the five classes:
+ *   ok          min(S, A)                         (:134 / :185)
+ *   unexpected  S if A == 0, else 0               (:137 / :190-193)
+ *   duplicated  max(S - A, 0) if A > 0, else 0    (:197-199; always 0 for a set)
+ *   lost        max(K - S, 0)                     (:140 / :203)
+ *   recovered   max(min(S, A) - K, 0)             (:144 / :207)
+ * K may exceed A (a completion without its invoke): the reference counts it so.
+ * Per class: count = the sum of the multiplicities, distinct = the values
+ * whose multiplicity is not zero, and the class as runs -- a run is a maximal
+ * stretch of consecutive integers v, v + 1, ... of one multiplicity, (lo, hi,
+ * mult), ascending (signed order; INT64_MAX is not followed by INT64_MIN),
+ * what util/integer-interval-set-str (jepsen/util.clj:483-508) prints for a
+ * set.  runs is exact; the first n_listed = min(runs, HSC_TALLY_LIST_CAP) are
+ * listed.  attempts / acks / seen: the distinct values of each input for a
+ * set, its elements with HSC_TALLY_MULTISET -- (count attempts) of the
+ * reference either way, the denominator of its fractions.  distinct: the
+ * distinct values of the three inputs together.  valid: no lost and no
+ * unexpected value (:146 / :209).  The caller decides what a history without a
+ * read means (:129-131); an empty seen is an empty read here.
+ * HSC_EINVAL: a NULL argument (an array may be NULL when its length is 0), a
+ * flag other than HSC_TALLY_MULTISET, or n_attempt + n_ack + n_seen >
+ * 0x7FFFFFFF: the sort carries each row's index in 32 bits and every position
+ * is scanned as a u32, the bound of the graph entries' op counts.
+ * HSC_EDEVICE: a host-only context.  Empty inputs succeed with valid = 1.
+ * The arrays are host memory owned by the context, never NULL, valid until
+ * the next hsc_tally_check on it.  Nothing a resolve, a build or any other
+ * entry left on the context is touched: the sort has rows of its own. */
+#define HSC_TALLY_MULTISET 1u
+#define HSC_TALLY_LIST_CAP 4096
+enum { HSC_TALLY_OK, HSC_TALLY_UNEXPECTED, HSC_TALLY_DUPLICATED, HSC_TALLY_LOST, HSC_TALLY_RECOVERED, HSC_TALLY_NCLASS };
+typedef struct hsc_tally_in {
+    size_t n_attempt, n_ack, n_seen;
+    const int64_t *attempt, *ack, *seen;
+} hsc_tally_in;
+typedef struct hsc_tally_class {
+    uint64_t count, distinct, runs;
+    uint32_t n_listed;             /* min(runs, HSC_TALLY_LIST_CAP) */
+    const int64_t *lo, *hi;        /* [n_listed] ascending */
+    const uint32_t *mult;          /* [n_listed] */
+} hsc_tally_class;
+typedef struct hsc_tally_report {
+    uint64_t attempts, acks, seen, distinct;
+    int valid;                     /* no lost, no unexpected */
+    hsc_tally_class cls[HSC_TALLY_NCLASS];
+    int sort_packed;               /* the (value, source) sort ran as packed single words */
+    float ms;                      /* device time of the whole call */
+} hsc_tally_report;
+int hsc_tally_check(hsc_ctx *ctx, const hsc_tally_in *in, unsigned flags, hsc_tally_report *out);
+/* hsc_bank_check is bank-checker (core.clj:152-177): read i holds the balances
+ * balance[off[i] .. off[i + 1]) of an :ok :read, n and total are the test's
+ * :model.  Per read, as the reference's cond: kind 1 (wrong-n) when its length
+ * is not n, found = the length, and its sum is not looked at; else kind 2
+ * (wrong-total) when its sum is not total; else 0; found = the sum for kinds 0
+ * and 2.  Sums wrap in 64 bits, where the reference's (reduce + balances)
+ * would throw an ArithmeticException (integer overflow) instead of answering.
+ * negatives[i]: the balances of read i below zero, whatever its kind;
+ * reads_with_negative: the reads with one.  Neither enters valid: the
+ * reference's checker does not look at signs (its docstring does; the client
+ * refuses a transfer that would go negative, :112-116), so a negative balance
+ * is reported but is not the verdict.  valid: no bad read.  The first n_listed
+ * = min(bad, HSC_BANK_LIST_CAP) bad reads are listed in read order.  A read
+ * may have any length, 0 included, whatever n is.
+ * HSC_EINVAL: a NULL argument (off and balance may be NULL when n_reads is 0,
+ * balance when off[n_reads] is 0), an off that does not start at 0 or
+ * descends, n_reads > 0x7FFFFFFF or off[n_reads] > 0xFFFFFFFF (the bad reads'
+ * positions and a read's negatives are u32).  HSC_EDEVICE: a host-only
+ * context.  n_reads == 0 succeeds with valid = 1.  The arrays are host memory
+ * owned by the context, never NULL, valid until the next hsc_bank_check. */
+#define HSC_BANK_LIST_CAP 4096
+typedef struct hsc_bank_in {
+    size_t n_reads;
+    const uint64_t *off;           /* [n_reads + 1] */
+    const int64_t *balance;        /* [off[n_reads]] */
+    uint64_t n;  int64_t total;    /* the model */
+} hsc_bank_in;
+typedef struct hsc_bank_report {
+    uint64_t n_reads, bad, wrong_n, wrong_total, reads_with_negative;
+    int valid;
+    const uint8_t *kind;           /* [n_reads] 0 fine, 1 wrong-n, 2 wrong-total */
+    const int64_t *found;          /* [n_reads] */
+    const uint32_t *negatives;     /* [n_reads] */
+    uint32_t n_listed;
+    const uint64_t *listed_read;   /* [n_listed] ascending */
+    float ms;                      /* device time of the whole call */
+} hsc_bank_report;
+int hsc_bank_check(hsc_ctx *ctx, const hsc_bank_in *in, hsc_bank_report *out);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst

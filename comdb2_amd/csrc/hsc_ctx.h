@@ -726,7 +726,7 @@ struct hsc_ctx {
     ListOut lists_out;
     InternalBufs internal;   // hsc_dep_graph_internal / _internal_lists: device scratch, host results
     InternalOut internal_out;
-    LinearBufs linear;       // hsc_linear_check: the device arena, host results
+    LinearBufs linear;       // hsc_linear_check / _wide: the device arena, the wide tables, host results
     LinearOut linear_out;
     TallyBufs tally;         // hsc_tally_check: device scratch and sort rows of its own, host results
     TallyOut tally_out;

@@ -3373,7 +3373,7 @@ int hsc_ctx_create(int device, hsc_ctx **out)
         if (!warmed[device]) {
             for (auto f : {warm_kernels, warm_ingest, warm_narrow, warm_ctiles, warm_delta,
                            warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_realtime, warm_anomaly, warm_si,
-                           warm_resolve, warm_lists, warm_internal, warm_linear, warm_tally, warm_route})
+                           warm_resolve, warm_lists, warm_internal, warm_linear, warm_linear_wide, warm_tally, warm_route})
                 (void)f();
             warmed[device] = true;
         }

@@ -918,7 +918,7 @@ constexpr uint32_t kLinTable = 8192;    // slots of the largest hash set (load <
 constexpr uint32_t kLinMinTable = 256;  // and of the smallest
 constexpr int kLinThreads = 512;
 constexpr uint32_t kLinEvBuf = 256;     // events of the program staged in LDS at a time
-struct alignas(16) LinEvent {  // w: bit 0 = return, bits 1-5 the slot, bits 8-9 f of a call; a, b: value ids
+struct alignas(16) LinEvent {  // w: bit 0 = return, bits 1-6 the slot (< 32 in the LDS tier's programs), bits 8-9 f of a call; a, b: value ids
     uint32_t w, a, b;
     uint32_t op;  // the history's op (the host's, for the report)
 };
@@ -936,18 +936,46 @@ struct LinResult {  // what the key's workgroup writes
 };
 struct LinearBufs {
     DBuf arena;  // events | keys | results | seen, one upload
-    void release_all() { arena.release(); }
+    DBuf wide;   // the wide tier's tables: a round's keys, 4 * max_configs words each
+    void release_all()
+    {
+        arena.release();
+        wide.release();
+    }
 };
 struct LinearOut {  // host results (hsc_lin_report points into them)
     std::vector<uint8_t> verdict, cause;
     std::vector<uint32_t> fail_op, prev_ok, peak, final_n;
     std::vector<uint64_t> state_off;
     std::vector<int64_t> state_val;
+    // per key, for the two-tier report: the events of its launched program, its expansions, the states
+    // of a BAD key's last set, the tier that judged it
+    std::vector<uint32_t> events;
+    std::vector<uint64_t> expanded;
+    std::vector<std::vector<int64_t>> states;
+    std::vector<uint8_t> tier;
 };
 // seen[key.seen_off + id] := 1 for the states of a BAD key's last set (zeroed by the caller)
 hipError_t linear_search(const LinEvent *prog, const LinKey *keys, uint32_t nkeys, LinResult *res, uint8_t *seen,
                          hipStream_t s);
 hipError_t warm_linear();
+// The wide tier (hsc_linear_wide.hip): the same search with the two hash sets
+// in device memory.  A configuration word is tag (bit 63) | state id (bits
+// 62-48) | mask of linearized pending slots (bits 47-0).
+constexpr uint32_t kLinWideSlots = 48;           // HSC_LIN_WIDE_SLOTS
+constexpr uint32_t kLinWideStates = 32767;       // HSC_LIN_WIDE_STATES: the ids 1 .. 2^15 - 1
+constexpr uint32_t kLinWideDefaultCap = 1u << 20;
+constexpr uint64_t kLinWideDefaultBudget = 1ull << 25;  // expansions per key (how it was chosen)
+constexpr uint64_t kLinWideDefaultArena = 1ull << 30;
+constexpr int kLinWideThreads = 1024;
+struct LinWideLimits {
+    uint32_t max_configs;   // a power of two; a key's two tables hold 2 * max_configs words each
+    uint64_t max_expanded;
+};
+// keys[0 .. nkeys) of one round, key b in tables + b * 4 * max_configs (cleared by the kernel)
+hipError_t linear_search_wide(const LinEvent *prog, const LinKey *keys, uint32_t nkeys, LinResult *res, uint8_t *seen,
+                              uint64_t *tables, const LinWideLimits &lim, hipStream_t s);
+hipError_t warm_linear_wide();
 // The accounting checkers (hsc_tally.hip).  Tally: three value
 // arrays -> per class the counts and the runs of consecutive values.  The
 // (value, source) sort goes through t, a set of sort rows of its own

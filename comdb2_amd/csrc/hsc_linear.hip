@@ -33,7 +33,7 @@
 //
 // Only LDS atomics (the 64-bit compare-and-swap of an insert, the counters);
 // the result words are plain stores of thread 0.
-#include "hsc_internal.h"
+#include "hsc_linear_dev.h"
 
 namespace hsc {
 
@@ -43,27 +43,6 @@ constexpr uint64_t kLinEmpty = ~0ull;
 constexpr uint64_t kLinTag = 1ull << 63;
 // control words in LDS
 enum { kCnt = 0, kOvf, kAlive, kExp, kDone, kAnd, kCtl };
-
-__device__ __forceinline__ uint32_t lin_hash(uint64_t key)
-{
-    uint32_t h = (uint32_t)key * 0x9E3779B1u ^ (uint32_t)(key >> 32) * 0x85EBCA6Bu;
-    return h ^ h >> 15;
-}
-
-// The op (f, a, b) on state st: legal?  *ns: the state after it.
-__device__ __forceinline__ bool lin_apply(uint32_t f, uint32_t a, uint32_t b, uint32_t st, uint32_t *ns)
-{
-    if (f == HSC_LIN_WRITE) {
-        *ns = a;
-        return true;
-    }
-    if (f == HSC_LIN_CAS) {
-        *ns = b;
-        return st == a;
-    }
-    *ns = st;  // a read: nil (id 0) matches any state
-    return a == 0 || a == st;
-}
 
 // key into t[size] unless it is there (the tag does not tell entries apart);
 // counted in ctl[kCnt].  More than `limit` entries, or no free slot: ctl[kOvf],

@@ -229,6 +229,26 @@ LIN_BAD, LIN_OK, LIN_UNKNOWN = 0, 1, 2
 LIN_CAUSE_SLOTS, LIN_CAUSE_CONFIGS = 1, 2
 
 
+class _LinWideLimits(C.Structure):
+    """hsc_lin_wide_limits."""
+    _fields_ = [("max_configs", C.c_uint32), ("flags", C.c_uint32), ("max_expanded", C.c_uint64),
+                ("arena_bytes", C.c_uint64)]
+
+
+class LinWideReport(C.Structure):
+    """hsc_lin_wide_report: the arrays are host memory of the context."""
+    _fields_ = [("base", LinReport), ("tier", _p), ("escalated", C.c_uint32), ("resolved", C.c_uint32),
+                ("rounds", C.c_uint32), ("wide_expanded", C.c_uint64), ("table_bytes", C.c_uint64),
+                ("wide_ms", C.c_float)]
+
+
+# hsc_linear_check_wide (include/hip_serial.h)
+LIN_WIDE_SLOTS, LIN_WIDE_STATES = 48, 32767
+LIN_WIDE_MIN_CAP, LIN_WIDE_MAX_CAP = 8192, 1 << 22
+LIN_CAUSE_BUDGET, LIN_CAUSE_STATES = 3, 4
+LIN_WIDE_ONLY = 1
+
+
 # hsc_tally_check / hsc_bank_check (include/hip_serial.h)
 TALLY_MULTISET = 1
 TALLY_LIST_CAP = BANK_LIST_CAP = 4096
@@ -346,7 +366,7 @@ EXPORTS = [
     "hsc_dep_graph_anomalies", "hsc_dep_graph_si",
     "hsc_dep_graph_resolve", "hsc_dep_graph_build_resolved", "hsc_dep_graph_resolve_sort_path",
     "hsc_dep_graph_resolve_lists", "hsc_dep_graph_build_lists",
-    "hsc_dep_graph_internal", "hsc_dep_graph_internal_lists", "hsc_linear_check",
+    "hsc_dep_graph_internal", "hsc_dep_graph_internal_lists", "hsc_linear_check", "hsc_linear_check_wide",
     "hsc_tally_check", "hsc_bank_check",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
@@ -445,6 +465,8 @@ def load() -> C.CDLL:
         "hsc_dep_graph_internal": (C.c_int, [_p, C.c_uint, C.POINTER(InternalReport)]),
         "hsc_dep_graph_internal_lists": (C.c_int, [_p, C.c_uint, C.POINTER(InternalReport)]),
         "hsc_linear_check": (C.c_int, [_p, C.POINTER(_LinOps), C.POINTER(LinReport)]),
+        "hsc_linear_check_wide": (C.c_int, [_p, C.POINTER(_LinOps), C.POINTER(_LinWideLimits),
+                                            C.POINTER(LinWideReport)]),
         "hsc_tally_check": (C.c_int, [_p, C.POINTER(_TallyIn), C.c_uint, C.POINTER(TallyReport)]),
         "hsc_bank_check": (C.c_int, [_p, C.POINTER(_BankIn), C.POINTER(BankReport)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
@@ -1454,6 +1476,14 @@ class Validator:
         the search held before the failing op, LIN_NIL among them as None),
         and the totals ``bad``, ``unknown``, ``events``, ``expanded``,
         ``dropped_open_reads``, ``ms``."""
+        s, keep = self._lin_ops(ops, init)
+        a = LinReport()
+        self._chk(self.lib.hsc_linear_check(self.ctx, C.byref(s), C.byref(a)), "hsc_linear_check")
+        return self._lin_report(a, s.nkeys)
+
+    @staticmethod
+    def _lin_ops(ops, init):
+        """(hsc_lin_ops over ``ops`` and ``init``, the arrays it points into)."""
         nkeys = int(ops["nkeys"])
         cols = {k: np.ascontiguousarray(ops[k], dt) for k, dt in
                 (("key", np.uint32), ("f", np.uint8), ("a", np.int64), ("b", np.int64),
@@ -1463,12 +1493,14 @@ class Validator:
             raise ValueError("the op arrays must be 1-d and of one length")
         s = _LinOps(nops=n, nkeys=nkeys, **{k: v.ctypes.data for k, v in cols.items()})
         if init is not None:
-            iv = np.ascontiguousarray(init, np.int64)
-            if iv.shape != (nkeys,):
+            cols["init"] = np.ascontiguousarray(init, np.int64)
+            if cols["init"].shape != (nkeys,):
                 raise ValueError("init must hold one value per key")
-            s.init = iv.ctypes.data
-        a = LinReport()
-        self._chk(self.lib.hsc_linear_check(self.ctx, C.byref(s), C.byref(a)), "hsc_linear_check")
+            s.init = cols["init"].ctypes.data
+        return s, cols
+
+    @staticmethod
+    def _lin_report(a, nkeys) -> dict:
         arr = _copy_out
         out = {k: getattr(a, k) for k in ("nkeys", "bad", "unknown", "events", "expanded", "dropped_open_reads", "ms")}
         for k, dt in (("verdict", np.uint8), ("cause", np.uint8), ("fail_op", np.uint32), ("prev_ok", np.uint32),
@@ -1478,6 +1510,32 @@ class Validator:
         vals = arr(a.state_val, int(off[-1]), np.int64)
         out["possible_values"] = [[None if v == LIN_NIL else int(v) for v in vals[int(off[k]):int(off[k + 1])]]
                                   for k in range(nkeys)]
+        return out
+
+    def linear_check_wide(self, ops, init=None, max_configs=None, max_expanded=None, arena_bytes=None,
+                          wide_only: bool = False) -> dict:
+        """``linear_check``, then the keys it leaves LIN_UNKNOWN for ``slots``
+        or ``configs`` searched again with the hash sets in device memory
+        (hsc_linear_check_wide): LIN_WIDE_SLOTS ops pending at once,
+        ``max_configs`` configurations alive inside a step (a power of two in
+        [LIN_WIDE_MIN_CAP, LIN_WIDE_MAX_CAP]; None: 2^20), LIN_WIDE_STATES
+        values on a key, ``max_expanded`` expansions per key (None: 2^25; past
+        them cause LIN_CAUSE_BUDGET), ``arena_bytes`` of device memory for the
+        tables of one launch round (None: 1 GiB).  ``wide_only``: skip the
+        first pass.  Returns ``linear_check``'s dict, every key's fields from
+        the tier that judged it, plus ``tier`` per key (1: the wide tier) and
+        ``escalated``, ``resolved``, ``rounds``, ``wide_expanded``,
+        ``table_bytes``, ``wide_ms``."""
+        s, keep = self._lin_ops(ops, init)
+        lim = _LinWideLimits(max_configs=int(max_configs or 0), flags=LIN_WIDE_ONLY if wide_only else 0,
+                             max_expanded=int(max_expanded or 0), arena_bytes=int(arena_bytes or 0))
+        a = LinWideReport()
+        self._chk(self.lib.hsc_linear_check_wide(self.ctx, C.byref(s), C.byref(lim), C.byref(a)),
+                  "hsc_linear_check_wide")
+        out = self._lin_report(a.base, s.nkeys)
+        out["tier"] = _copy_out(a.tier, s.nkeys, np.uint8)
+        out.update({k: getattr(a, k) for k in ("escalated", "resolved", "rounds", "wide_expanded", "table_bytes",
+                                               "wide_ms")})
         return out
 
     def tally_check(self, attempt, ack, seen, multiset: bool = False) -> dict:

@@ -991,7 +991,7 @@ def check_dirty_reads_edn(validator, text: str, n: Optional[int] = None) -> dict
 LIN_READ, LIN_WRITE, LIN_CAS = 0, 1, 2   # hsc_linear_check's f
 LIN_NIL = -(1 << 63)                     # HSC_LIN_NIL
 LIN_BAD, LIN_OK, LIN_UNKNOWN = 0, 1, 2   # its verdicts
-LIN_CAUSES = {0: None, 1: "slots", 2: "configs"}
+LIN_CAUSES = {0: None, 1: "slots", 2: "configs", 3: "budget", 4: "states"}
 _LIN_F = {":read": LIN_READ, ":write": LIN_WRITE, ":cas": LIN_CAS}
 
 
@@ -1099,7 +1099,9 @@ def linear_report(ops: LinOps, res: dict) -> dict:
     completion whose return left no configuration), ``previous_ok`` (the key's
     last completion before it) and ``possible_values`` (what the register could
     hold before it; None = nil), ``peak_configs``, ``final_configs`` -- and the
-    counts and ``ms``."""
+    counts and ``ms``.  Of ``Validator.linear_check_wide``'s dict also each
+    key's ``tier`` (1: judged by the wide tier; its cause may then be "budget"
+    or "states") and ``escalated``, ``resolved``, ``wide_ms``."""
     names = {LIN_BAD: False, LIN_OK: True, LIN_UNKNOWN: "unknown"}
     keys = {}
     for k, name in enumerate(ops.keys):
@@ -1110,25 +1112,36 @@ def linear_report(ops: LinOps, res: dict) -> dict:
                       "previous_ok": ops.completions[po] if bad and po != 0xFFFFFFFF else None,
                       "possible_values": res["possible_values"][k] if bad else None,
                       "peak_configs": int(res["peak_configs"][k]), "final_configs": int(res["final_configs"][k])}
+        if "tier" in res:
+            keys[name]["tier"] = int(res["tier"][k])
     report = {"valid": False if res["bad"] else "unknown" if res["unknown"] else True, "keys": keys,
               "ok": ops.ok, "failed": ops.failed, "info": ops.info, "unpaired": ops.unpaired}
     report.update({k: res[k] for k in ("bad", "unknown", "events", "expanded", "dropped_open_reads", "ms")})
+    if "tier" in res:
+        report.update({k: res[k] for k in ("escalated", "resolved", "wide_ms")})
     return report
 
 
-def check_linear_edn(validator, text: str, init=None, independent: bool = False) -> dict:
+def check_linear_edn(validator, text: str, init=None, independent: bool = False, wide=False) -> dict:
     """knossos' checker/linearizable over cas-register-comdb2 through the GPU:
     :func:`lin_ops_from_register_edn`, ``Validator.linear_check``,
     :func:`linear_report` (plus ``history``, the :class:`LinOps`).  ``init``:
     the registers' initial value (None: nil), or a dict from history key to
-    it."""
+    it.  ``wide``: True, or a dict of ``Validator.linear_check_wide``'s keyword
+    arguments (``max_configs``, ``max_expanded``, ``arena_bytes``,
+    ``wide_only``): the keys whose search leaves LDS are searched again in
+    device memory instead of coming out "unknown"."""
     ops = lin_ops_from_register_edn(text, independent)
     if init is None:
         iv = None
     else:
         per = init if isinstance(init, dict) else {k: init for k in ops.keys}
         iv = np.array([LIN_NIL if per.get(k) is None else int(per[k]) for k in ops.keys], np.int64)
-    report = linear_report(ops, validator.linear_check(ops.arrays(), iv))
+    if wide is False or wide is None:
+        res = validator.linear_check(ops.arrays(), iv)
+    else:
+        res = validator.linear_check_wide(ops.arrays(), iv, **(wide if isinstance(wide, dict) else {}))
+    report = linear_report(ops, res)
     report["history"] = ops
     return report
 

@@ -1283,6 +1283,57 @@ typedef struct hsc_lin_report {
 } hsc_lin_report;
 int hsc_linear_check(hsc_ctx *ctx, const hsc_lin_ops *ops, hsc_lin_report *out);
 
+/* The wide tier: hsc_linear_check, then the keys it leaves HSC_LIN_UNKNOWN for
+ * `slots` or `configs` searched again from their first event with the two hash
+ * sets in device memory (one workgroup per key; DESIGN.md §5j "The wide
+ * tier").  The step, the event order and the lowest-free-slot rule are the
+ * same; the caps are HSC_LIN_WIDE_SLOTS ops pending at once, max_configs
+ * configurations alive inside one step and HSC_LIN_WIDE_STATES distinct
+ * non-nil values on the key (the state id is 15 bits of the configuration
+ * word; cause HSC_LIN_CAUSE_STATES, the key is not launched).  A key the first
+ * pass judges OK or BAD keeps those fields, bit for bit, with tier 0; an
+ * escalated key has tier 1 and every field from the wide search, its events
+ * and expansions in base.events and base.expanded in place of the first
+ * pass's.  HSC_LIN_WIDE_ONLY skips the first pass: every key with events goes
+ * wide.
+ * Budget: after every completed step, a key whose expansions so far exceed
+ * max_expanded is HSC_LIN_UNKNOWN / HSC_LIN_CAUSE_BUDGET with peak and final
+ * as of the steps done.  A step expands at most max_configs entries and the
+ * counts are of sets, so the verdict is deterministic and the launch bounded.
+ * The default, 2^25, is 5.7 s of one key's worst case at the 5.9 M expansions/s
+ * measured.
+ * One key's tables take table_bytes = 32 * max_configs device bytes; a launch
+ * round searches arena_bytes / table_bytes keys.
+ * HSC_EINVAL as hsc_linear_check, and for a max_configs that is not a power of
+ * two in [HSC_LIN_WIDE_MIN_CAP, HSC_LIN_WIDE_MAX_CAP], unknown flags, or a
+ * non-zero arena_bytes below table_bytes.  The report's arrays are owned by
+ * the context until its next linear call of either kind. */
+#define HSC_LIN_WIDE_SLOTS    48          /* ops pending at once in the wide tier */
+#define HSC_LIN_WIDE_MIN_CAP  8192u       /* max_configs: a power of two in [MIN, MAX] */
+#define HSC_LIN_WIDE_MAX_CAP  (1u << 22)
+#define HSC_LIN_WIDE_STATES   32767       /* distinct non-nil values of one key in the wide tier */
+#define HSC_LIN_CAUSE_BUDGET  3           /* max_expanded passed */
+#define HSC_LIN_CAUSE_STATES  4           /* more than HSC_LIN_WIDE_STATES values on the key */
+#define HSC_LIN_WIDE_ONLY     1u          /* flags: skip the LDS tier, every key with events goes wide */
+typedef struct hsc_lin_wide_limits {
+    uint32_t max_configs;    /* 0: default 1 << 20 */
+    uint32_t flags;
+    uint64_t max_expanded;   /* per key; 0: default 1 << 25 */
+    uint64_t arena_bytes;    /* device bytes for wide tables per round; 0: default 1 GiB */
+} hsc_lin_wide_limits;
+typedef struct hsc_lin_wide_report {
+    hsc_lin_report base;       /* as hsc_linear_check's, every key's fields from the tier that judged it */
+    const uint8_t *tier;       /* [nkeys] 0: LDS tier (or no events), 1: wide tier */
+    uint32_t escalated;        /* keys sent to the wide tier */
+    uint32_t resolved;         /* of them, no longer UNKNOWN */
+    uint32_t rounds;           /* wide launches */
+    uint64_t wide_expanded;
+    uint64_t table_bytes;      /* device bytes of one key's wide tables */
+    float wide_ms;             /* device time of the wide rounds; base.ms is the whole call */
+} hsc_lin_wide_report;
+int hsc_linear_check_wide(hsc_ctx *ctx, const hsc_lin_ops *ops, const hsc_lin_wide_limits *limits /* NULL: defaults */,
+                          hsc_lin_wide_report *out);
+
 /* ---- the accounting checkers: set, total-queue, bank -------------------------
  * The other two workloads of the reference's Jepsen suite
  * (linearizable/jepsen/src/comdb2/core.clj: set-client and sets-test :223-272,

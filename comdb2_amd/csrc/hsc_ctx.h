@@ -1,7 +1,8 @@
 // hsc_ctx.h -- the validator context (struct hsc_ctx) and the host-side
 // types it holds, shared by hsc_host.cpp (single-GPU context),
-// hsc_graph_host.cpp (its dependency-graph entries) and hsc_multi.cpp (the
-// multi-GPU context built from member contexts).
+// hsc_probe_host.cpp (its probe dispatch), hsc_graph_host.cpp and its
+// neighbours (the history checkers' entries) and hsc_multi.cpp (the multi-GPU
+// context built from member contexts).
 #pragma once
 #include "../../include/hip_serial.h"
 #include "hsc_internal.h"
@@ -114,6 +115,36 @@ inline StageLayout stage_layout(int W, size_t n, size_t nl)
     L.lock_txn = o, o = al(o + 4 * nl);
     L.total = o;
     return L;
+}
+
+// The probe batch over a StageLayout arena at base: n ranges, nl table locks
+// (n_txn, verdict and bitmap are the caller's to set).
+inline hsc_probe_batch stage_batch(const void *base, const StageLayout &L, size_t n, size_t nl)
+{
+    const uint8_t *a = (const uint8_t *)base;
+    hsc_probe_batch b{};
+    b.n = n;
+    b.lo = (const uint64_t *)(a + L.lo);
+    b.hi = (const uint64_t *)(a + L.hi);
+    b.gid = (const uint32_t *)(a + L.gid);
+    b.snap = (const uint64_t *)(a + L.snap);
+    b.txn = (const uint32_t *)(a + L.txn);
+    b.n_lock = nl;
+    b.lock_table = (const uint32_t *)(a + L.lock_table);
+    b.lock_snap = (const uint64_t *)(a + L.lock_snap);
+    b.lock_txn = (const uint32_t *)(a + L.lock_txn);
+    return b;
+}
+
+// A batch's columns as the kernels take them.
+inline ProbeView batch_view(const hsc_probe_batch &b)
+{
+    ProbeView p{};
+    p.lo = b.lo, p.hi = b.hi, p.gid = b.gid, p.snap = b.snap, p.txn = b.txn;
+    p.lock_table = b.lock_table, p.lock_snap = b.lock_snap, p.lock_txn = b.lock_txn;
+    p.n = (uint32_t)b.n;
+    p.n_lock = (uint32_t)b.n_lock;
+    return p;
 }
 
 // Room a small batch's slot needs past the columns: the verdict bytes and the
@@ -812,8 +843,9 @@ struct hsc_ctx {
 };
 
 namespace hsc {
-// hsc_host.cpp internals the multi-GPU context (hsc_multi.cpp) drives its
-// member contexts with
+// hsc_host.cpp internals the other host files reach the context through: the
+// multi-GPU context (hsc_multi.cpp) drives its member contexts with them, the
+// probe dispatch (hsc_probe_host.cpp) takes its lane and its delta runs
 int ctx_fail(hsc_ctx *c, int code, const char *what, hipError_t e = hipSuccess);
 // A failed HIP call ends the function with HSC_EDEVICE and the call's text as
 // the context's error; a failed hsc call (rc != HSC_OK) with its rc.
@@ -833,7 +865,16 @@ int ctx_ensure_built(hsc_ctx *c);
 void ctx_add_write(hsc_ctx *c, int tid, int ix, const uint8_t *key, int keylen, bool has_key, uint64_t lsn);
 int ctx_flush_appends(hsc_ctx *c, bool lazy = false);
 void ctx_raise_table_max(hsc_ctx *c, int tid, uint64_t lsn);
+// Make the lane of c->stream active / note a batch of the active lane on it.
+hipError_t select_lane(hsc_ctx *c);
+void lane_mark(hsc_ctx *c);
+// the live and the frozen delta run (c->dn, c->fn rows)
+DeltaView delta_view(const hsc_ctx *c);
+DeltaView frozen_view(const hsc_ctx *c);
+// (hsc_probe_host.cpp) Probe batch b on the built window, on c->stream
+// (callers hold c->mu); the last timed batch's legs and counts into c->last.
 int ctx_probe(hsc_ctx *c, const hsc_probe_batch *b);
+int collect_timing(hsc_ctx *c);
 // c->stream := s, the active lane's batches on the stream left fenced by its
 // done event first (callers hold c->mu)
 hipError_t ctx_switch_stream(hsc_ctx *c, hipStream_t s);

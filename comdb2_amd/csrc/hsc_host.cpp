@@ -9,7 +9,8 @@
 //     currangearr_build_hash + serial_check_callback (db/sqlglue.c:312-351,
 //     db/glue.c:2926-2963) and the min-length memcmp padding lemma;
 //   * the drop-in entry points bdb_osql_serial_check / check_batch.
-// There is no CPU verdict path: every range verdict comes from the GPU join.
+// There is no CPU verdict path: every range verdict comes from the GPU join,
+// which hsc_probe_host.cpp launches for the batches marshalled here.
 #include "../../include/hip_serial.h"
 #include "hsc_internal.h"
 
@@ -45,7 +46,7 @@ static_assert(sizeof kLaneBufs / sizeof kLaneBufs[0] <= 20, "Lane::b size");
 
 // Make the lane of c->stream active (the least recently used lane if the
 // stream has none).
-static hipError_t select_lane(hsc_ctx *c)
+hipError_t hsc::select_lane(hsc_ctx *c)
 {
     int want = -1;
     for (int i = 0; i < hsc_ctx::kLanes; ++i)
@@ -91,7 +92,7 @@ static hipError_t lane_done(hsc_ctx *c)
 // A batch of the active lane went onto c->stream: its done event is recorded
 // when the context leaves the stream (lane_leave) -- a take-over of the lane
 // or a window change from another stream happens only after that.
-static void lane_mark(hsc_ctx *c) { c->lanes[c->lane].pend = true; }
+void hsc::lane_mark(hsc_ctx *c) { c->lanes[c->lane].pend = true; }
 
 static hipError_t lane_leave(hsc_ctx *c)
 {
@@ -1125,7 +1126,7 @@ static int stage_appends(hsc_ctx *c, int W, size_t *k_out, int nt = 0)
     return HSC_OK;
 }
 
-static DeltaView delta_view(const hsc_ctx *c)
+DeltaView hsc::delta_view(const hsc_ctx *c)
 {
     DeltaView d{};
     d.gid = c->d_dgid[c->dcur].as<uint32_t>();
@@ -1466,7 +1467,7 @@ static void swap_window(hsc_ctx *a, hsc_ctx *b)
     swap(a->d_cph, b->d_cph), swap(a->cph_nb, b->cph_nb), swap(a->cph_ep, b->cph_ep);
 }
 
-static DeltaView frozen_view(const hsc_ctx *c)
+DeltaView hsc::frozen_view(const hsc_ctx *c)
 {
     DeltaView d{};
     d.gid = c->f_dgid.as<uint32_t>();
@@ -2424,583 +2425,8 @@ static int marshal_readsets(hsc_ctx *c, const hsc_readsets *rs)
 }
 
 // ---------------------------------------------------------------------------
-// device probe
+// device probe of a marshalled batch (the dispatch: hsc_probe_host.cpp)
 // ---------------------------------------------------------------------------
-static WinView win_view(hsc_ctx *c)
-{
-    WinView w{};
-    w.words = c->d_words.as<uint64_t>();
-    w.stride = c->cap;
-    w.lsn = c->d_lsn.as<uint64_t>();
-    w.gid = c->d_gid.as<uint32_t>();
-    w.gstart = c->d_gstart.as<uint32_t>();
-    w.gend = c->d_gend.as<uint32_t>();
-    w.tmax = c->d_tmax.as<uint64_t>();
-    w.table_max = c->d_table_max.as<uint64_t>();
-    w.sp_g = c->d_sp_g.as<uint32_t>();
-    w.sp_w = c->d_sp_w.as<uint64_t>();
-    w.n = (uint32_t)c->n;
-    w.ntiles = c->ntiles;
-    w.ntables = (uint32_t)c->table_names.size();
-    w.W = c->W;
-    w.log2T = c->log2T;
-    w.levels = c->levels;
-    w.gbits = 0;
-    while (w.gbits < 32 && ((size_t)1 << w.gbits) < c->groups.size()) w.gbits++;
-    return w;
-}
-
-static int probe_delta(hsc_ctx *c, uint8_t *target);
-// the batch's delta probe will mark verdict bytes (then a pack pass builds the bitmap)
-static bool pack_after_delta(const hsc_ctx *c) { return c->raw_probe.n && (c->fn || c->dn); }
-
-// Narrow layout: one kernel answers every range and table lock.
-static int probe_narrow(hsc_ctx *c, const hsc_probe_batch *b, const WinView &w,
-                        const ProbeView &p)
-{
-    hipStream_t s = c->stream;
-    NarrowView nv = c->nv;
-    nv.table_max = w.table_max;
-    nv.ntables = w.ntables;
-    const bool tm = c->timing;
-    if (tm)
-        for (int i = 0; i < 6; ++i)
-            if (!c->ev[i]) HIPCHK(c, hipEventCreate(&c->ev[i]));
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    if (b->n_txn) HIPCHK(c, hipMemsetAsync(b->verdict, 0, b->n_txn, s));
-    // timing slots: locate = verdict clear, plan = scatter = 0, join = the probe
-    if (tm)
-        for (int i = 1; i <= 3; ++i) HIPCHK(c, hipEventRecord(c->ev[i], s));
-    HIPCHK(c, launch_probe_narrow(nv, p, b->verdict, s));
-    HIPCHK_RC(c, probe_delta(c, b->verdict));
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[4], s));
-    HIPCHK(c, launch_pack(b->verdict, (uint32_t)b->n_txn, b->bitmap, s));
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[5], s));
-    return HSC_OK;
-}
-
-static int probe_tiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &w, const ProbeView &p,
-                       bool started = false);
-
-#ifdef HSC_STAMPS
-// Diagnostic builds: phase durations of the locate (np0 stamps) and the join
-// (np1 stamps), median over blocks, in shader cycles; clears the stamps.
-static int stamp_report(hsc_ctx *c, const ProbeWork &work, uint32_t max_items, int np0, int np1)
-{
-    hipStream_t s = c->stream;
-    if (!work.stamps) return HSC_OK;
-    std::vector<uint64_t> h(2 * 8192 * 8);
-    HIPCHK(c, hipMemcpyAsync(h.data(), work.stamps, 8 * h.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    const uint32_t nb[2] = {8 * ((work.G + 7) / 8), max_items};
-    const int np[2] = {np0, np1};
-    for (int k = 0; k < 2; ++k) {
-        fprintf(stderr, "[stamps] %s blocks %u:", k ? "join" : "locate", nb[k]);
-        uint64_t t0 = ~0ull, t1 = 0;
-        for (uint32_t b = 0; b < nb[k] && b < 8192; ++b) {
-            const uint64_t *r = &h[((size_t)k * 8192 + b) * 8];
-            if (!r[0]) continue;
-            t0 = std::min(t0, r[0]);
-            t1 = std::max(t1, r[np[k] - 1]);
-        }
-        for (int q = 1; q < np[k]; ++q) {
-            std::vector<uint64_t> d;
-            for (uint32_t b = 0; b < nb[k] && b < 8192; ++b) {
-                const uint64_t *r = &h[((size_t)k * 8192 + b) * 8];
-                if (r[q] && r[q - 1]) d.push_back(r[q] - r[q - 1]);
-            }
-            std::sort(d.begin(), d.end());
-            fprintf(stderr, " p%d %llu", q, d.empty() ? 0ull : (unsigned long long)d[d.size() / 2]);
-        }
-        std::vector<uint64_t> st;
-        for (uint32_t b = 0; b < nb[k] && b < 8192; ++b) {
-            const uint64_t *r = &h[((size_t)k * 8192 + b) * 8];
-            if (r[0]) st.push_back(r[0] - t0);
-        }
-        std::sort(st.begin(), st.end());
-        fprintf(stderr, " | span %llu, start p50 %llu p90 %llu\n", (unsigned long long)(t1 - t0),
-                st.empty() ? 0ull : (unsigned long long)st[st.size() / 2],
-                st.empty() ? 0ull : (unsigned long long)st[st.size() * 9 / 10]);
-    }
-    HIPCHK(c, hipMemsetAsync(work.stamps, 0, 8 * h.size(), s));
-    return HSC_OK;
-}
-
-static DBuf &stamp_buffer()
-{
-    static DBuf b;
-    return b;
-}
-#endif
-
-// Narrow tiles (dense batch): locate (codes, snapshot ranks, per-chunk tile
-// histograms) -> column scan + plan -> scatter (16-byte records) -> join
-// (8-byte rows) -> pack.
-static int probe_ntiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &wn,
-                        const ProbeView &p)
-{
-    hipStream_t s = c->stream;
-    c->probe_ntiles = wn.ntiles;
-    c->probe_buckets = true;
-    const uint32_t nt = std::max<uint32_t>(wn.ntiles, 1);
-    ProbeWork work{};
-    work.lds_mode = 1;
-    const size_t nwork = std::max<size_t>(p.n, p.n_lock);
-    // chunks of narrow_tiles_chunk() probes (at most kMaxChunks: the caller
-    // sends larger batches down the code-tile path)
-    work.chunk = narrow_tiles_chunk();
-    work.G = (uint32_t)std::max<size_t>(1, (nwork + work.chunk - 1) / work.chunk);
-    const size_t n1 = std::max<uint32_t>(p.n, 1);
-    HIPCHK(c, c->w_hist.ensure(4 * (size_t)hist_stride(work.G) * nt));
-    // tile buckets of kTileCap records, then the overflow area (at most 2n
-    // records spill); join items: one per tile + the overflow chunks (each hot
-    // tile rounds its own run up: at most 2 ceil(2n / kJoinChunk) of them)
-    HIPCHK(c, c->w_counts.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_bucket.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_items.ensure(4 * std::max<size_t>((size_t)nt + 1, 4)));
-    const uint32_t extra_items = 2 * (uint32_t)((2 * n1 + kJoinChunk - 1) / kJoinChunk);
-    const uint32_t max_items = nt + extra_items;
-    HIPCHK(c, c->w_item_desc.ensure(16 * (size_t)extra_items + 16));
-    // chunk-sorted records: each chunk's records in an area of its own, tile
-    // runs found by the join through the plan's scan (no scatter pass)
-    HIPCHK(c, c->w_tcode2.ensure(2 * (size_t)hist_stride(work.G) * nt));  // cst
-    // chunk-major rows of {kept records' run and count, located records}
-    const size_t cm_words = (size_t)work.G * ((nt + 3) & ~3u);
-    HIPCHK(c, c->w_tcode.ensure(8 * cm_words));
-    HIPCHK(c, c->w_trecs.ensure(16 * 2 * (size_t)work.chunk * work.G));
-    work.cst = c->w_tcode2.as<uint16_t>();
-    work.hist = c->w_hist.as<uint32_t>();
-    work.counts = c->w_counts.as<uint32_t>();
-    work.bucket_off = c->w_bucket.as<uint32_t>();
-    work.cursor = c->w_cursor.as<uint32_t>();
-    work.item_off = c->w_items.as<uint32_t>();
-    work.item_tile = c->w_item_tile.as<uint32_t>();
-    work.item_desc = c->w_item_desc.as<uint4>();
-#ifdef HSC_STAMPS
-    DBuf &stamp_buf = stamp_buffer();
-    if (getenv("HSC_STAMPS")) {
-        if (!stamp_buf.p) {
-            HIPCHK(c, stamp_buf.ensure(8 * 2 * 8192 * 8));
-            HIPCHK(c, hipMemsetAsync(stamp_buf.p, 0, 8 * 2 * 8192 * 8, s));
-        }
-        work.stamps = stamp_buf.as<uint64_t>();
-    }
-#endif
-    NarrowTiles ntl{};
-    ntl.key32 = c->d_key32.as<uint32_t>();
-    ntl.rank32 = c->d_rank32.as<uint32_t>();
-    ntl.rank_lsn32 = c->rank_lsn32;
-    ntl.rank_base = c->rank_base;
-    ntl.cdir = c->cdir;
-    ntl.tdir = c->tdir;
-    ntl.trad = c->trad_m ? c->d_trad.as<uint32_t>() : nullptr;
-    ntl.trad_m = c->trad_m;
-    ntl.trad16 = c->trad_m ? c->d_trad16.as<uint16_t>() : nullptr;
-    ntl.trad_shift = c->trad_shift;
-    ntl.recs = c->w_trecs.as<uint4>();
-    narrow_recent_view(ntl, c->d_recent.as<uint32_t>(), wn.ntiles, c->slot_qshift);
-    if (!c->d_fulljoins.p) {
-        HIPCHK(c, c->d_fulljoins.ensure(8));
-        HIPCHK(c, hipMemset(c->d_fulljoins.p, 0, 8));
-    }
-    work.full_joins = c->d_fulljoins.as<uint32_t>();
-    work.wave_fallbacks = work.full_joins + 1;
-    // conflict flags: internal, all zero between batches (the pack clears them)
-    const size_t had = c->w_vflags.bytes;
-    HIPCHK(c, c->w_vflags.ensure((std::max<size_t>(b->n_txn, 1) + 15) & ~(size_t)15));
-    if (c->w_vflags.bytes != had) HIPCHK(c, hipMemsetAsync(c->w_vflags.p, 0, c->w_vflags.bytes, s));
-    uint8_t *flags = c->w_vflags.as<uint8_t>();
-    // The batch's path.  Balanced window: no plan -- the locate clears the
-    // verdict bytes, the join scans its tiles' columns, runs a tile of more
-    // than kTileCap records in rounds inside its one block and moves the
-    // flags.  The plan and its overflow blocks stay for a skewed window (the
-    // bucket table in log mode) and while a batch of the last kHotBatches had
-    // such a tile: the kernels of either path store the batch's number into
-    // the hot word, which is read here as it stands (a late store only delays
-    // the switch; both paths give the same verdicts).
-    const bool joins = p.n && wn.ntiles;
-    const bool delta = pack_after_delta(c);
-    bool column = false;
-    if (joins) {
-        if (!c->h_hot.p) {  // two words: hot, wide (hsc_ctx.h)
-            if (c->h_hot.ensure(16, true, true)) return fail(c, HSC_ENOMEM, "hot word");
-            c->h_hot.as<volatile uint64_t>()[0] = 0;
-            c->h_hot.as<volatile uint64_t>()[1] = 0;
-        }
-        work.hot = (uint64_t *)c->h_hot.dp;
-        work.wide = work.hot + 1;
-        work.batch = ++c->nt_batch;
-        const uint64_t hot = *c->h_hot.as<volatile uint64_t>();
-        column = !c->trad_log && !(hot && work.batch - hot <= hsc_ctx::kHotBatches);
-        (column ? c->nt_column : c->nt_plan)++;
-    }
-    if (column) {
-        work.vout = b->verdict;
-        work.n_txn = (uint32_t)b->n_txn;
-        work.bitmap = delta ? nullptr : b->bitmap;
-    }
-    const bool tm = c->timing;
-    if (tm)
-        for (int i = 0; i < 6; ++i)
-            if (!c->ev[i]) HIPCHK(c, hipEventCreate(&c->ev[i]));
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    // the table's layout goes with the locate instance: two-word entries
-    // where its filter makes located != kept, one word otherwise
-    if (narrow_locate_fast(c->nv, ntl, p))
-        work.cmx = c->w_tcode.as<uint2>();
-    else
-        work.cm = c->w_tcode.as<uint32_t>();
-    int shape = -1;
-    HIPCHK(c, launch_locate_t(c->nv, wn, p, work, ntl, flags, s, &shape));
-    if (shape >= 0) (shape ? c->nt_fast : c->nt_general)++;
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[1], s));
-    if (column) {
-        // (no plan, no scatter: their legs of the timing are empty)
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[2], s));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        // a wave per tile for what a fast locate's filter left, unless a batch
-        // of the last kHotBatches was wide (the word as it stands: a late
-        // store only delays the switch, both joins give the same verdicts)
-        const uint64_t wide = c->h_hot.as<volatile uint64_t>()[1];
-        const bool wave = work.cmx && !(wide && work.batch - wide <= hsc_ctx::kHotBatches);
-        (wave ? c->nt_wave : c->nt_block)++;
-        if (wave)
-            HIPCHK(c, launch_join_wave(work, ntl, wn.n, wn.ntiles, flags, s));
-        else
-            HIPCHK(c, launch_join_col(work, ntl, wn.n, wn.ntiles, flags, s));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[4], s));
-        HIPCHK_RC(c, probe_delta(c, b->verdict));
-        if (delta) HIPCHK(c, launch_pack(b->verdict, (uint32_t)b->n_txn, b->bitmap, s));
-    } else if (joins) {
-        // the plan writes the verdict bytes (and bitmap words) from the
-        // locate's flags; the join and the delta probe then mark the verdict
-        // itself, the join its bitmap bits too (no pack pass unless the delta
-        // probe ran: it marks bytes only)
-        work.bitmap = delta ? nullptr : b->bitmap;
-        HIPCHK(c, launch_plan_s(work, wn.ntiles, c->w_items.as<uint32_t>(), s, flags,
-                                (uint32_t)b->n_txn, b->verdict));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[2], s));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        // blocks past the tiles for the hot tiles' overflow items: 512, or 2048
-        // on a skewed window (the bucket table took log mode: Zipf keys crowd
-        // a few tiles -- r03: config 5 one stream 83 -> 80 us with 2048, while
-        // config 2's idle extra blocks cost its overlapped batch)
-        const uint32_t extra = c->trad_log ? 2048u : 512u;
-        HIPCHK(c, launch_join_t(work, ntl, wn.n, wn.ntiles, max_items, b->verdict, s, extra));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[4], s));
-        HIPCHK_RC(c, probe_delta(c, b->verdict));
-        if (delta) HIPCHK(c, launch_pack(b->verdict, (uint32_t)b->n_txn, b->bitmap, s));
-    } else {
-        if (tm)
-            for (int i = 2; i <= 4; ++i) HIPCHK(c, hipEventRecord(c->ev[i], s));
-        HIPCHK_RC(c, probe_delta(c, flags));
-        HIPCHK(c, launch_pack_flags(flags, (uint32_t)b->n_txn, b->verdict, b->bitmap, s));
-    }
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[5], s));
-#ifdef HSC_STAMPS
-    HIPCHK_RC(c, stamp_report(c, work, max_items, 6, 4));
-#endif
-    return HSC_OK;
-}
-
-// Compact tiles (dense or sparse batch over a compact window): code bounds
-// (compact_probes) -> locate (gid || code keys, end tiles, 64-byte probe
-// entries) -> plan -> scatter (4-byte bucket entries) -> join -> pack.
-static int probe_ctiles(hsc_ctx *c, const hsc_probe_batch *b, const ProbeView &p)
-{
-    hipStream_t s = c->stream;
-    const WinView w = win_view(c);
-    CTiles ct = c->ctv;
-    c->probe_ntiles = ct.ntiles;
-    c->probe_buckets = true;
-    const uint32_t nt = std::max<uint32_t>(ct.ntiles, 1);
-    ProbeWork work{};
-    work.lds_mode = 1;
-    work.chunk = ctiles_chunk();
-    work.G = (uint32_t)std::max<size_t>(1, (std::max<size_t>(p.n, p.n_lock) + work.chunk - 1) / work.chunk);
-    const size_t n1 = std::max<uint32_t>(p.n, 1);
-    const int WC = c->ct.WC;
-    HIPCHK(c, c->p_code_lo.ensure(8 * (size_t)WC * n1));
-    HIPCHK(c, c->p_code_hi.ensure(8 * (size_t)WC * n1));
-    HIPCHK(c, c->w_hist.ensure(4 * (size_t)hist_stride(work.G) * nt));
-    HIPCHK(c, c->w_counts.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_bucket.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_items.ensure(4 * std::max<size_t>((size_t)nt + 1, 4)));
-    const uint32_t extra_items = 2 * (uint32_t)((2 * n1 + kJoinChunk - 1) / kJoinChunk);
-    const uint32_t max_items = nt + extra_items;
-    HIPCHK(c, c->w_item_desc.ensure(16 * (size_t)extra_items + 16));
-    // chunk-sorted 64-byte records (the read set number shares its word with
-    // the record kind: the caller sends batches of >= 2^30 read sets down the
-    // wide pipeline)
-    HIPCHK(c, c->w_tcode.ensure(4 * (size_t)work.G * ((nt + 3) & ~3u)));  // chunk-major rows
-    HIPCHK(c, c->w_tcode2.ensure(2 * (size_t)hist_stride(work.G) * nt));  // run starts
-    HIPCHK(c, c->w_trecs.ensure(64 * 2 * (size_t)work.chunk * work.G));
-    work.cm = c->w_tcode.as<uint32_t>();
-    work.cst = c->w_tcode2.as<uint16_t>();
-    work.hist = c->w_hist.as<uint32_t>();
-    work.counts = c->w_counts.as<uint32_t>();
-    work.bucket_off = c->w_bucket.as<uint32_t>();
-    work.item_off = c->w_items.as<uint32_t>();
-    work.item_desc = c->w_item_desc.as<uint4>();
-    ct.recs = c->w_trecs.as<uint32_t>();
-    ct.np = p.n;
-#ifdef HSC_STAMPS
-    DBuf &stamp_buf = stamp_buffer();
-    if (getenv("HSC_STAMPS")) {
-        if (!stamp_buf.p) {
-            HIPCHK(c, stamp_buf.ensure(8 * 2 * 8192 * 8));
-            HIPCHK(c, hipMemsetAsync(stamp_buf.p, 0, 8 * 2 * 8192 * 8, s));
-        }
-        work.stamps = stamp_buf.as<uint64_t>();
-    }
-#endif
-    const size_t had = c->w_vflags.bytes;
-    HIPCHK(c, c->w_vflags.ensure((std::max<size_t>(b->n_txn, 1) + 15) & ~(size_t)15));
-    if (c->w_vflags.bytes != had) HIPCHK(c, hipMemsetAsync(c->w_vflags.p, 0, c->w_vflags.bytes, s));
-    uint8_t *flags = c->w_vflags.as<uint8_t>();
-    WinView wt = c->wc;  // tile maxima of the same 2048-row tiles
-    wt.table_max = w.table_max;
-    wt.ntables = w.ntables;
-    const bool tm = c->timing;
-    if (tm)
-        for (int i = 0; i < 6; ++i)
-            if (!c->ev[i]) HIPCHK(c, hipEventCreate(&c->ev[i]));
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    // (measured: the bound mapping fused into the locate -- code bounds kept in
-    // registers -- ran 83 us against 67 us for the two kernels on config 3)
-    PointHash ph{};
-    if (c->cph_nb) {
-        ph.e = c->d_cph.as<uint64_t>();
-        ph.nb = c->cph_nb;
-        ph.WG = ct.WG;
-        ph.gb = ct.gb;
-        ph.rank_base = ct.rank_base;
-        ph.flags = flags;
-        ph.ep = c->cph_ep;
-    }
-    if (p.n)
-        HIPCHK(c, compact_probes(p, c->ct, c->p_code_lo.as<uint64_t>(), c->p_code_hi.as<uint64_t>(), s, &ph));
-    HIPCHK(c, launch_locate_c(ct, wt, p, c->p_code_lo.as<uint64_t>(), c->p_code_hi.as<uint64_t>(),
-                              work, flags, s));
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[1], s));
-    if (p.n && ct.ntiles) {
-        // verdict bytes and bitmap from the plan and the join, as probe_ntiles
-        const bool delta = pack_after_delta(c);
-        work.bitmap = delta ? nullptr : b->bitmap;
-        HIPCHK(c, launch_plan_s(work, ct.ntiles, c->w_items.as<uint32_t>(), s, flags,
-                                (uint32_t)b->n_txn, b->verdict));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[2], s));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        HIPCHK(c, launch_join_c(ct, work, max_items, b->verdict, s));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[4], s));
-        HIPCHK_RC(c, probe_delta(c, b->verdict));
-        if (delta) HIPCHK(c, launch_pack(b->verdict, (uint32_t)b->n_txn, b->bitmap, s));
-    } else {
-        if (tm)
-            for (int i = 2; i <= 4; ++i) HIPCHK(c, hipEventRecord(c->ev[i], s));
-        HIPCHK_RC(c, probe_delta(c, flags));
-        HIPCHK(c, launch_pack_flags(flags, (uint32_t)b->n_txn, b->verdict, b->bitmap, s));
-    }
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[5], s));
-#ifdef HSC_STAMPS
-    HIPCHK_RC(c, stamp_report(c, work, max_items, 2, 7));
-#endif
-    return HSC_OK;
-}
-
-static int probe_lane(hsc_ctx *c, const hsc_probe_batch *b);
-static int probe(hsc_ctx *c, const hsc_probe_batch *b)
-{
-    if (c->host_only) return fail(c, HSC_EDEVICE, "host-only context");
-    if (c->pend_n || c->pend_t) HIPCHK_RC(c, flush_appends(c));  // the pending tail is k_small_narrow's only
-    HIPCHK(c, select_lane(c));
-    const int rc = probe_lane(c, b);
-    // the lane's done event fences whatever probe_lane launched, also when it
-    // failed part way: a later take-over of the lane or a window rebuild from
-    // another stream waits on it before touching the lane's scratch; it is
-    // recorded when the context leaves this stream (ctx_switch_stream)
-    lane_mark(c);
-    return rc;
-}
-
-// Range probes of the batch against the delta run (appends since the last
-// build) into the path's verdict target, before its pack.
-static int probe_delta(hsc_ctx *c, uint8_t *target)
-{
-    if (!c->raw_probe.n) return HSC_OK;
-    if (c->fn) HIPCHK(c, launch_probe_delta(frozen_view(c), c->raw_probe, target, c->stream));
-    if (c->dn) HIPCHK(c, launch_probe_delta(delta_view(c), c->raw_probe, target, c->stream));
-    return HSC_OK;
-}
-
-static int probe_lane(hsc_ctx *c, const hsc_probe_batch *b)
-{
-    const WinView w = win_view(c);
-    if (b->n > 0xFFFFFFFFull / 2 || b->n_lock > 0xFFFFFFFFull || b->n_txn > 0xFFFFFFFFull)
-        return fail(c, HSC_EINVAL, "batch too large");
-    ProbeView p{};
-    p.lo = b->lo;
-    p.hi = b->hi;
-    p.gid = b->gid;
-    p.snap = b->snap;
-    p.txn = b->txn;
-    p.lock_table = b->lock_table;
-    p.lock_snap = b->lock_snap;
-    p.lock_txn = b->lock_txn;
-    p.n = w.n ? (uint32_t)b->n : 0;  // empty key window: no range can match
-    p.n_lock = (uint32_t)b->n_lock;
-    c->raw_probe = p;
-    c->raw_probe.n = (uint32_t)b->n;  // the delta may hold keys of an empty main window
-    // compact tiles for dense batches; a sparse one (fewer than kDirectPerTile
-    // ranges per tile) takes the wide pipeline, which stages only the tiles
-    // its ranges reach (the compact-tile join stages every tile)
-    if (!c->narrow && c->compact && c->ctiles && c->layout != HSC_LAYOUT_COMPACT_WIDE &&
-        p.n < (1u << 30) && b->n_txn < (1u << 30) && (size_t)p.n >= kDirectPerTile * (size_t)c->ctv.ntiles &&
-        (std::max<size_t>(p.n, p.n_lock) + ctiles_chunk() - 1) / ctiles_chunk() <= (size_t)kMaxChunks)
-        return probe_ctiles(c, b, p);
-    if (!c->narrow && c->compact) {
-        // wide keys as compact codes: map the bounds, then the tile pipeline
-        const int WC = c->ct.WC;
-        const size_t n = std::max<uint32_t>(p.n, 1);
-        HIPCHK(c, c->p_code_lo.ensure(8 * (size_t)WC * n));
-        HIPCHK(c, c->p_code_hi.ensure(8 * (size_t)WC * n));
-        if (c->timing) {
-            if (!c->ev[0]) HIPCHK(c, hipEventCreate(&c->ev[0]));
-            HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        }
-        HIPCHK(c, compact_probes(p, c->ct, c->p_code_lo.as<uint64_t>(), c->p_code_hi.as<uint64_t>(),
-                                 c->stream));
-        ProbeView pc = p;
-        pc.lo = c->p_code_lo.as<uint64_t>();
-        pc.hi = c->p_code_hi.as<uint64_t>();
-        WinView wc = c->wc;
-        wc.table_max = w.table_max;
-        wc.ntables = w.ntables;
-        wc.gbits = w.gbits;
-        return probe_tiles(c, b, wc, pc, c->timing);
-    }
-    if (!c->narrow) return probe_tiles(c, b, w, p);
-    // narrow window: a sparse batch is answered by the direct probe; a dense
-    // one maps its bounds to codes and runs the tile pipeline on the codes
-    const bool direct = c->layout == HSC_LAYOUT_NARROW_DIRECT ||
-                        (c->layout != HSC_LAYOUT_NARROW_TILES &&
-                         (size_t)p.n < kDirectPerTile * (size_t)c->wn.ntiles);
-    if (direct) {
-        c->probe_ntiles = 0;
-        return probe_narrow(c, b, w, p);
-    }
-    WinView wn = c->wn;
-    wn.table_max = w.table_max;
-    wn.ntables = w.ntables;
-    // 8-byte tile rows when they fit and the batch fits one column scan
-    const size_t nchunks = (std::max<size_t>(p.n, p.n_lock) + narrow_tiles_chunk() - 1) /
-                           narrow_tiles_chunk();
-    if (c->ntiles32 && c->layout != HSC_LAYOUT_NARROW_CODES && nchunks <= (size_t)kMaxChunks)
-        return probe_ntiles(c, b, wn, p);
-    const size_t n = std::max<uint32_t>(p.n, 1);
-    HIPCHK(c, c->p_code_lo.ensure(8 * n));
-    HIPCHK(c, c->p_code_hi.ensure(8 * n));
-    const size_t zb = c->p_zero.bytes;
-    HIPCHK(c, c->p_zero.ensure(4 * n));
-    if (c->p_zero.bytes != zb) HIPCHK(c, hipMemsetAsync(c->p_zero.p, 0, c->p_zero.bytes, c->stream));
-    NarrowView nv = c->nv;
-    HIPCHK(c, narrow_codes(nv, p, c->p_code_lo.as<uint64_t>(), c->p_code_hi.as<uint64_t>(),
-                           c->stream));
-    ProbeView pn = p;
-    pn.lo = c->p_code_lo.as<uint64_t>();
-    pn.hi = c->p_code_hi.as<uint64_t>();
-    pn.gid = c->p_zero.as<uint32_t>();
-    return probe_tiles(c, b, wn, pn);
-}
-
-// The tile pipeline: locate -> plan -> scatter -> join -> pack.
-// started: ev[0] was recorded by the caller (a bound transform before locate
-// counts as locate time).
-static int probe_tiles(hsc_ctx *c, const hsc_probe_batch *b, const WinView &w, const ProbeView &p,
-                       bool started)
-{
-    hipStream_t s = c->stream;
-    c->probe_ntiles = w.ntiles;
-    c->probe_buckets = false;
-    const uint32_t nt = std::max<uint32_t>(w.ntiles, 1);
-    ProbeWork work{};
-    work.lds_mode = w.ntiles <= (uint32_t)kHistCap;
-    const size_t nwork = std::max<size_t>(p.n, p.n_lock);
-    work.G = (uint32_t)std::min<size_t>(kMaxChunks, std::max<size_t>(1, (nwork + 2047) / 2048));
-    work.chunk = (uint32_t)((p.n + work.G - 1) / work.G);
-    HIPCHK(c, c->w_code.ensure(8 * (size_t)std::max<uint32_t>(p.n, 1)));
-    HIPCHK(c, c->w_hist.ensure(4 * (size_t)work.G * nt));
-    HIPCHK(c, c->w_counts.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_bucket.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_cursor.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_items.ensure(4 * ((size_t)nt + 1)));
-    HIPCHK(c, c->w_recs.ensure(8 * (size_t)rec_words(w.W) * 2 * std::max<uint32_t>(p.n, 1)));
-    const uint32_t max_items = nt + (uint32_t)((2 * (size_t)p.n + kJoinChunk - 1) / kJoinChunk);
-    HIPCHK(c, c->w_item_tile.ensure(4 * (size_t)max_items + 16));
-    HIPCHK(c, c->w_item_desc.ensure(16 * (size_t)max_items + 16));
-    work.item_desc = c->w_item_desc.as<uint4>();
-    work.code = c->w_code.as<uint64_t>();
-    work.hist = c->w_hist.as<uint32_t>();
-    work.counts = c->w_counts.as<uint32_t>();
-    work.bucket_off = c->w_bucket.as<uint32_t>();
-    work.cursor = c->w_cursor.as<uint32_t>();
-    work.item_off = c->w_items.as<uint32_t>();
-    work.item_tile = c->w_item_tile.as<uint32_t>();
-    work.recs = c->w_recs.as<uint64_t>();
-    const bool tm = c->timing;
-    if (tm)
-        for (int i = 0; i < 6; ++i)
-            if (!c->ev[i]) HIPCHK(c, hipEventCreate(&c->ev[i]));
-    if (tm && !started) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    if (b->n_txn) HIPCHK(c, hipMemsetAsync(b->verdict, 0, b->n_txn, s));
-    if (!work.lds_mode) HIPCHK(c, hipMemsetAsync(c->w_counts.p, 0, 4 * ((size_t)nt + 1), s));
-    HIPCHK(c, launch_locate(w, p, work, b->verdict, s));
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[1], s));
-    if (p.n && w.ntiles) {
-        HIPCHK(c, launch_plan(w, work, s));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[2], s));
-        HIPCHK(c, launch_scatter(w, p, work, s));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        HIPCHK(c, launch_join(w, work, max_items, b->verdict, s));
-        if (tm) HIPCHK(c, hipEventRecord(c->ev[4], s));
-    } else if (tm) {
-        HIPCHK(c, hipEventRecord(c->ev[2], s));
-        HIPCHK(c, hipEventRecord(c->ev[3], s));
-        HIPCHK(c, hipEventRecord(c->ev[4], s));
-    }
-    HIPCHK_RC(c, probe_delta(c, b->verdict));
-    HIPCHK(c, launch_pack(b->verdict, (uint32_t)b->n_txn, b->bitmap, s));
-    if (tm) HIPCHK(c, hipEventRecord(c->ev[5], s));
-    return HSC_OK;
-}
-
-static int collect_timing(hsc_ctx *c)
-{
-    if (!c->timing || !c->ev[5]) return HSC_OK;
-    HIPCHK(c, hipEventSynchronize(c->ev[5]));
-    float t[5];
-    for (int i = 0; i < 5; ++i) (void)hipEventElapsedTime(&t[i], c->ev[i], c->ev[i + 1]);
-    c->last.locate_ms = t[0];
-    c->last.plan_ms = t[1];
-    c->last.scatter_ms = t[2];
-    c->last.join_ms = t[3];
-    c->last.pack_ms = t[4];
-    (void)hipEventElapsedTime(&c->last.probe_total_ms, c->ev[0], c->ev[5]);
-    uint64_t nrec = 0;
-    if (c->probe_ntiles && c->w_counts.p && c->probe_buckets) {  // per-tile record counts
-        std::vector<uint32_t> cnt(c->probe_ntiles);
-        HIPCHK(c, hipMemcpy(cnt.data(), c->w_counts.p, 4 * cnt.size(), hipMemcpyDeviceToHost));
-        for (uint32_t v : cnt) nrec += v;
-    } else if (c->probe_ntiles && c->w_bucket.p) {
-        uint32_t r = 0;
-        HIPCHK(c, hipMemcpy(&r, c->w_bucket.as<uint32_t>() + c->probe_ntiles, 4, hipMemcpyDeviceToHost));
-        nrec = r;
-    }
-    c->last.records = nrec;
-    c->last.tiles = c->probe_ntiles;  // tiles of the view the last probe joined over
-    return HSC_OK;
-}
-
 // Upload staging set st (pinned), run the join, download the verdict bytes
 // into st.verdict -- all asynchronous on c->stream; st.done marks the end.
 static int launch_stage(hsc_ctx *c, Stage &st)
@@ -3012,22 +2438,10 @@ static int launch_stage(hsc_ctx *c, Stage &st)
     if (st.verdict.ensure(std::max<size_t>(st.n_txn, 1), true)) return fail(c, HSC_ENOMEM, "staging");
     if (st.n || st.n_lock)  // every column in one transfer
         HIPCHK(c, hipMemcpyAsync(c->p_arena.p, st.arena.p, st.L.total, hipMemcpyHostToDevice, s));
-    auto dcol = [&](size_t off) { return (void *)((uint8_t *)c->p_arena.p + off); };
-    hsc_probe_batch b{};
-    b.n = st.n;
-    b.lo = (const uint64_t *)dcol(st.L.lo);
-    b.hi = (const uint64_t *)dcol(st.L.hi);
-    b.gid = (const uint32_t *)dcol(st.L.gid);
-    b.snap = (const uint64_t *)dcol(st.L.snap);
-    b.txn = (const uint32_t *)dcol(st.L.txn);
-    b.n_lock = st.n_lock;
-    b.lock_table = (const uint32_t *)dcol(st.L.lock_table);
-    b.lock_snap = (const uint64_t *)dcol(st.L.lock_snap);
-    b.lock_txn = (const uint32_t *)dcol(st.L.lock_txn);
+    hsc_probe_batch b = stage_batch(c->p_arena.p, st.L, st.n, st.n_lock);
     b.n_txn = st.n_txn;
     b.verdict = c->p_verdict.as<uint8_t>();
-    b.bitmap = nullptr;
-    const int rc = probe(c, &b);
+    const int rc = ctx_probe(c, &b);
     if (rc) return rc;
     if (st.n_txn)
         HIPCHK(c, hipMemcpyAsync(st.verdict.p, c->p_verdict.p, st.n_txn, hipMemcpyDeviceToHost, s));
@@ -3123,17 +2537,7 @@ static int small_launch(hsc_ctx *c, Stage &st)
     *done = 0;
     std::atomic_thread_fence(std::memory_order_seq_cst);
     ProbeView &p = sl.p;
-    p = ProbeView{};
-    p.lo = (const uint64_t *)(dio + st.L.lo);
-    p.hi = (const uint64_t *)(dio + st.L.hi);
-    p.gid = (const uint32_t *)(dio + st.L.gid);
-    p.snap = (const uint64_t *)(dio + st.L.snap);
-    p.txn = (const uint32_t *)(dio + st.L.txn);
-    p.lock_table = (const uint32_t *)(dio + st.L.lock_table);
-    p.lock_snap = (const uint64_t *)(dio + st.L.lock_snap);
-    p.lock_txn = (const uint32_t *)(dio + st.L.lock_txn);
-    p.n = (uint32_t)st.n;
-    p.n_lock = (uint32_t)st.n_lock;
+    p = batch_view(stage_batch(dio, st.L, st.n, st.n_lock));
     static const bool empty = getenv("HSC_SMALL_EMPTY") != nullptr;  // diagnostics: the
     if (empty) p.n = p.n_lock = 0;  // launch + done-word floor (verdicts all 0: wrong answers)
     sl.nv = c->nv;
@@ -4582,7 +3986,7 @@ int hsc_probe_device(hsc_ctx *c, const hsc_probe_batch *b)
     MuGuard g(c);
     if (!c->host_only) (void)hipSetDevice(c->device);
     if (c->dirty) return fail(c, HSC_ESTATE, "window not built");
-    return probe(c, b);
+    return ctx_probe(c, b);
 }
 
 int hsc_pack_verdicts(hsc_ctx *c, const uint8_t *verdict, size_t n_txn, uint64_t *bitmap)
@@ -4641,7 +4045,6 @@ void ctx_add_write(hsc_ctx *c, int tid, int ix, const uint8_t *key, int keylen, 
 }
 int ctx_flush_appends(hsc_ctx *c, bool lazy) { return flush_appends(c, lazy); }
 void ctx_raise_table_max(hsc_ctx *c, int tid, uint64_t lsn) { raise_table_max(c, tid, lsn); }
-int ctx_probe(hsc_ctx *c, const hsc_probe_batch *b) { return probe(c, b); }
 int ctx_default_threads() { return default_threads(); }
 void ctx_par_for(hsc_ctx *c, int nwork, const std::function<void(int)> &f) { par_for(c, true, nwork, f, true); }
 

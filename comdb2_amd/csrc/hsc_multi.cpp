@@ -533,22 +533,6 @@ static RouteTarget block_target(uint8_t *b, int W, size_t n, size_t nl)
     return t;
 }
 
-static hsc_probe_batch arena_batch(uint8_t *base, const StageLayout &L, size_t n, size_t nl)
-{
-    hsc_probe_batch b{};
-    b.n = n;
-    b.lo = (const uint64_t *)(base + L.lo);
-    b.hi = (const uint64_t *)(base + L.hi);
-    b.gid = (const uint32_t *)(base + L.gid);
-    b.snap = (const uint64_t *)(base + L.snap);
-    b.txn = (const uint32_t *)(base + L.txn);
-    b.n_lock = nl;
-    b.lock_table = (const uint32_t *)(base + L.lock_table);
-    b.lock_snap = (const uint64_t *)(base + L.lock_snap);
-    b.lock_txn = (const uint32_t *)(base + L.lock_txn);
-    return b;
-}
-
 static hsc_probe_batch view_batch(const ProbeView &p)
 {
     hsc_probe_batch b{};
@@ -922,7 +906,7 @@ static int run_pipeline(hsc_ctx *f, int L, MSource *src, bool shared)
     for (int m = 0; m < NL; ++m) {
         MLane &ml = M->lane[L][m];
         const int d = M->rank + m;
-        in[m] = arena_batch(ml.recv.as<uint8_t>(), ml.recvL, nd[d], d == 0 ? nlock : 0);
+        in[m] = stage_batch(ml.recv.p, ml.recvL, nd[d], d == 0 ? nlock : 0);
     }
     MRC(probe_merge(f, L, in, tb.data(), outs));
     const auto t4 = SteadyClock::now();

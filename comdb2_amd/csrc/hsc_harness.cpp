@@ -204,8 +204,19 @@ int hsc_harness_commit_protocol(hsc_ctx *ctx, const hsc_protocol_txn *txns, int 
             const int t = ~e;
             while (!begun[t].load(std::memory_order_acquire)) std::this_thread::yield();
             const hsc_protocol_txn &x = txns[t];
-            if (x.nwrites <= 0) continue;  // read-only: never checked (db/sqloffload.c:280-287)
             hsc_currangearr *a = (hsc_currangearr *)x.arr;
+            if (x.nwrites <= 0) {
+                // read-only: never checked (db/sqloffload.c:280-287), unless it holds a selectv
+                // array: that one full check, outside the commit protocol
+                // (selectv_range_commit, db/sqloffload.c:505-524); nothing is logged
+                if (!x.selectv || a->size <= 0) continue;
+                const auto f0 = clk::now();
+                const int rc = hip_bdb_osql_serial_check(ctx, a, &a->file, &a->offset, 0);
+                L.full.push_back(us(f0, clk::now()));
+                check_end_out[t] = ((uint64_t)a->file << 32) | a->offset;
+                if (rc) rc_out[t] = 1, L.aborts++;
+                continue;
+            }
             const auto c0 = clk::now();
             pthread_rwlock_rdlock(&commit_lock);
             pthread_rwlock_unlock(&commit_lock);

@@ -324,7 +324,7 @@ class JoinStats(C.Structure):
 
 class ProtocolTxn(C.Structure):
     """hsc_protocol_txn: one txn of the commit-protocol harness."""
-    _fields_ = [("arr", _p), ("writes", _p), ("nwrites", C.c_int)]
+    _fields_ = [("arr", _p), ("writes", _p), ("nwrites", C.c_int), ("selectv", C.c_int)]
 
 
 class ProtocolResult(C.Structure):
@@ -978,7 +978,8 @@ class Validator:
         """db/toblock.c:4757-4836 replayed natively (hsc_harness_commit_protocol)
         by nthreads threads over events [('begin' | 'commit', workloads.Txn)]:
         snapshots taken at begin, commits through the commit_lock protocol
-        (regop probe under the write lock, full check outside it, append).
+        (regop probe under the write lock, full check outside it, append); a
+        selectv txn without writes gets its one full check and logs nothing.
         -> (rc int32[n], commit_seq int64[n], snap u64[n], check_end u64[n],
         stats dict); txns indexed as in `txns`."""
         from .formats import DTA_TYPES
@@ -1004,6 +1005,7 @@ class Validator:
             pt[i].arr = ptrs[i]
             pt[i].writes = C.cast(ws, _p)
             pt[i].nwrites = len(t.writes)
+            pt[i].selectv = int(getattr(t, "selectv", False))
         ev = np.array([idx[t.name] if e == "begin" else ~idx[t.name] for e, t in events], np.int32)
         rc = np.zeros(max(1, n), np.int32)
         seq = np.zeros(max(1, n), np.int64)

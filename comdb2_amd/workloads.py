@@ -190,6 +190,15 @@ class Txn:
     name: str
     reads: List[Range]
     writes: List[Tuple[int, str, int, Optional[bytes]]]  # (rectype, table, ix, key)
+    selectv: bool = False  # reads are a selectv array: checked at commit even without writes
+
+
+def commit_checked(t: Txn) -> bool:
+    """Whether a commit of t runs the check: a write txn ships its read set
+    (read-only txns never do, db/sqloffload.c:280-287,357-363); a selectv txn
+    is checked whether it wrote or not, unless its array is empty
+    (selectv_range_commit, db/sqloffload.c:505-524)."""
+    return bool(t.writes) or (t.selectv and bool(t.reads))
 
 
 def replay(events: Sequence[Tuple[str, Txn]], check: Callable[[LLog, ReadSets], np.ndarray],
@@ -197,7 +206,8 @@ def replay(events: Sequence[Tuple[str, Txn]], check: Callable[[LLog, ReadSets], 
     """events: ('begin', txn) / ('commit', txn) in time order.  At begin the
     snapshot is the end-of-log LSN (bdb_get_current_lsn, bdb/tran.c:2662).  At
     commit a write txn is checked (read-only txns never ship a read set,
-    db/sqloffload.c:280-287,357-363); if serializable its writes are logged
+    db/sqloffload.c:280-287,357-363) and so is a selectv txn with a read set
+    (:func:`commit_checked`); if serializable its writes, if any, are logged
     as one committed txn.  Returns {txn name: rc} for checked txns."""
     lb = LogBuilder(tbnames)
     snaps, rcs = {}, {}
@@ -205,13 +215,13 @@ def replay(events: Sequence[Tuple[str, Txn]], check: Callable[[LLog, ReadSets], 
         if ev == "begin":
             snaps[t.name] = lb.next_lsn()
             continue
-        if not t.writes:
+        if not commit_checked(t):
             continue
         log = lb.build()
         rs = ReadSets.from_lists([t.reads], [snaps[t.name]], tbnames=lb.tbnames)
         rc = int(check(log, rs)[0])
         rcs[t.name] = rc
-        if rc == 0:
+        if rc == 0 and t.writes:
             lb.begin(t.name)
             for rt, tb, ix, key in t.writes:
                 lb.write(t.name, rt, tb, ix, key)
@@ -223,7 +233,8 @@ def replay_incremental(events: Sequence[Tuple[str, Txn]], v, tbnames: Sequence[s
                        mode: str = "log", on_check=None, check_times=None) -> dict:
     """The commit stream of :func:`replay` against one validator whose window
     is kept up to date incrementally: an empty log is ingested once, then
-    every passing write txn's records are appended -- as the continuation of
+    every passing write txn's records are appended (a selectv txn without
+    writes is checked and appends nothing) -- as the continuation of
     the log (``mode="log"``: hsc_window_append_log, the chains decoded on the
     device side's host decoder) or as decoded writes (``mode="writes"``:
     hsc_window_append + hsc_window_set_end).  Each check is the drop-in entry
@@ -238,7 +249,7 @@ def replay_incremental(events: Sequence[Tuple[str, Txn]], v, tbnames: Sequence[s
         if ev == "begin":
             snaps[t.name] = lb.next_lsn()
             continue
-        if not t.writes:
+        if not commit_checked(t):
             continue
         arrs = CurRangeArrays([t.reads], [snaps[t.name]])
         if on_check:
@@ -248,7 +259,7 @@ def replay_incremental(events: Sequence[Tuple[str, Txn]], v, tbnames: Sequence[s
         if check_times is not None:
             check_times.append(time.perf_counter() - t0)
         rcs[t.name] = rc
-        if rc == 0:
+        if rc == 0 and t.writes:
             start = len(lb.rows)
             lb.begin(t.name)
             for rt, tb, ix, key in t.writes:

@@ -1508,6 +1508,12 @@ typedef struct hsc_protocol_txn {
     void *arr;                /* CurRangeArr* (file / offset set at begin)   */
     const hsc_write *writes;  /* the txn's writes (commit_lsn ignored)       */
     int nwrites;
+    int selectv;              /* arr is a selectv array: a txn without writes
+                                 is still checked (one full check, no lock,
+                                 db/sqloffload.c:505-524: rc_out 1 if it
+                                 conflicts, check_end_out its end) unless arr
+                                 is empty; it logs nothing, commit_seq -1.
+                                 0: a txn without writes is never checked    */
 } hsc_protocol_txn;
 typedef struct hsc_protocol_result {
     double seconds;           /* first event to last commit                  */

@@ -22,6 +22,46 @@ def serialstep():
         return json.load(f)
 
 
+def selectv_range():
+    """{scenario name: scenario} of tests/golden/selectv_range.json"""
+    with open(os.path.join(GOLDEN, "selectv_range.json")) as f:
+        return json.load(f)
+
+
+def selectv_cases():
+    """[(scenario name, variant name, scenario with the variant's read sets in
+    place)] of selectv_range.json, in name order."""
+    out = []
+    for name, sc in sorted(selectv_range().items()):
+        for vname, over in sorted(sc["variants"].items()):
+            txns = {n: dict(t, reads=over.get(n, t["reads"])) for n, t in sc["txns"].items()}
+            out.append((name, vname, dict(sc, txns=txns)))
+    return out
+
+
+def selectv_events(sc, snapshot="begin"):
+    """The scenario's replay events.  A ["read", txn] event marks the txn's
+    last read statement: snapshot="begin" drops it (the reference's snapshot,
+    taken when the transaction begins), snapshot="last_read" begins the txn
+    there instead."""
+    assert snapshot in ("begin", "last_read")
+    reads_at = {n for ev, n in sc["events"] if ev == "read"}
+    keep = []
+    for ev, n in sc["events"]:
+        if ev == "read":
+            if snapshot == "last_read":
+                keep.append(["begin", n])
+        elif not (ev == "begin" and snapshot == "last_read" and n in reads_at):
+            keep.append([ev, n])
+    return scenario_events(dict(sc, events=keep))
+
+
+def commit_verdicts(sc, rcs):
+    """Per commit statement of the scenario, in order: 1 if the replay's rc
+    says it failed; a txn that was not checked passed."""
+    return [int(rcs.get(n, 0) != 0) for n in sc["commits"]]
+
+
 def scenario_events(sc):
     txns = {}
     for name, t in sc["txns"].items():
@@ -30,7 +70,7 @@ def scenario_events(sc):
                        r["lflag"], r["rflag"], r["islocked"]) for r in t["reads"]]
         writes = [(WRITE_TYPES[w[0]], w[1], w[2], None if w[3] is None else bytes.fromhex(w[3]))
                   for w in t["writes"]]
-        txns[name] = Txn(name, reads, writes)
+        txns[name] = Txn(name, reads, writes, bool(t.get("selectv", False)))
     return [(ev, txns[n]) for ev, n in sc["events"]]
 
 

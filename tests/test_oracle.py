@@ -1,13 +1,16 @@
 """CPU: pin the oracle (C restatement of bdb_osql_serial_check) against the
 reference's own known answers (tests/serialstep.test, restated in
-tests/golden/serialstep.json) and against an independent set-formula model."""
+tests/golden/serialstep.json; tests/selectv_range.test and
+tests/selectv_recom_range.test, restated in tests/golden/selectv_range.json)
+and against an independent set-formula model."""
 import numpy as np
 import pytest
 
 from comdb2_amd import formats as F
 from comdb2_amd.formats import LogBuilder, Range, ReadSets
-from comdb2_amd.workloads import config1_events, config2, random_case, replay
-from helpers import model_check, scenario_events, serialstep
+from comdb2_amd.workloads import Txn, config1_events, config2, random_case, replay
+from helpers import (commit_verdicts, model_check, scenario_events, selectv_cases, selectv_events,
+                     selectv_range, serialstep)
 
 
 def oracle_checker(o):
@@ -27,6 +30,115 @@ def test_serialstep_model_agrees():
     for name, sc in serialstep().items():
         rcs = replay(scenario_events(sc), lambda log, rs: model_check(log, rs)[0])
         assert sorted(t for t, rc in rcs.items() if rc) == sorted(sc["expect_fail"]), name
+
+
+SELECTV = [pytest.param(sc, id=f"{name}-{vname}") for name, vname, sc in selectv_cases()]
+
+
+@pytest.fixture(scope="module")
+def host_checker():
+    """The host path of DESIGN §5c as a checker.  A host-only context refuses
+    check_readsets (tests/test_marshal.py), so the verdict is the native
+    marshaller's forced verdicts or'ed with the probe-level model of the join
+    over the batch it marshalled."""
+    from comdb2_amd.hsc import Validator
+    from probe_model import WindowModel, evaluate
+    v = Validator(-1)
+
+    def check(log, rs):
+        v.ingest_log(log)
+        m = v.marshal(rs)
+        return (evaluate(v, m, WindowModel(log)) | m["forced"]) != 0
+    yield check
+    v.close()
+
+
+def selectv_checkers(oracle_mod, host_checker):
+    return {"oracle": oracle_checker(oracle_mod), "model": lambda log, rs: model_check(log, rs)[0],
+            "host": host_checker}
+
+
+@pytest.mark.parametrize("sc", SELECTV)
+def test_selectv_range_known_answers(oracle_mod, host_checker, sc):
+    """tests/golden/selectv_range.json: the ordered commit verdicts of every
+    scenario and variant equal the reference's, by the C oracle, the set-formula
+    model and the host path; with the read set as captured and coalesced
+    (oracle/coalesce_oracle.c); with the snapshot at begin (the reference's) and
+    just after the txn's last read."""
+    for who, check in selectv_checkers(oracle_mod, host_checker).items():
+        for form in ("raw", "coalesced"):
+            chk = check if form == "raw" else (lambda log, rs, c=check: c(log, oracle_mod.coalesce(rs)))
+            for snapshot in ("begin", "last_read"):
+                rcs = replay(selectv_events(sc, snapshot), chk)
+                assert commit_verdicts(sc, rcs) == sc["reference_commits"], (who, form, snapshot, rcs)
+                # what was checked: every selectv txn with a read set, and every write txn
+                want = {n for n, t in sc["txns"].items() if t["writes"] or (t["selectv"] and t["reads"])}
+                assert set(rcs) == want, (who, form, snapshot)
+
+
+def test_selectv_range_fixture_shape():
+    """20 commits, 10 failing; every situation the issue names is present."""
+    cases = selectv_range()
+    commits = [v for sc in cases.values() for v in sc["reference_commits"]]
+    assert (len(commits), sum(commits)) == (20, 10)
+    for name, sc in cases.items():
+        assert len(sc["commits"]) == len(sc["reference_commits"]), name
+        assert sc["reference_commits"] == [int(n in sc["expect_fail"]) for n in sc["commits"]], name
+    txns = [(n, t) for sc in cases.values() for n, t in sc["txns"].items()]
+    assert any(t["selectv"] and t["reads"] and not t["writes"] for _, t in txns)   # read-only, checked
+    assert any(not t["selectv"] and not t["reads"] and not t["writes"] for _, t in txns)  # never checked
+    keyless = cases["range.t5_08"]["txns"]["B1"]["writes"]
+    assert [w[0] for w in keyless] == ["upd_dta"]                                   # a data record only
+
+
+@pytest.mark.parametrize("kind", ["narrow", "wide"])
+def test_selectv_matrix_verdicts_hold_by_construction(oracle_mod, host_checker, kind):
+    """tests/selectv_matrix.py at a small tile size: the filler changes no
+    scenario verdict and every decoy's verdict is the constructed one -- by
+    the oracle, the model (one offset) and the host path."""
+    import selectv_matrix as M
+    windows = M.build(64, kind)
+    assert len(windows) == 3 * 24                   # 24 checked commits over all variants, 3 offsets
+    for i, w in enumerate(windows):
+        assert w.pool.ntxn == M.POOL and w.want[1:].any() and not w.want[1:].all()
+        np.testing.assert_array_equal(oracle_mod.check(w.log, w.pool)[0] != 0, w.want,
+                                      err_msg=f"oracle: {w.what}")
+        np.testing.assert_array_equal(host_checker(w.log, w.pool), w.want, err_msg=f"host: {w.what}")
+        if i % 3 == 0:
+            np.testing.assert_array_equal(model_check(w.log, w.pool)[0] != 0, w.want,
+                                          err_msg=f"model: {w.what}")
+    # 10 failing commits, and the second variants of recom.t5_01 (1) and recom.t6_01 (3) again
+    assert sum(w.want[0] for w in windows) == 3 * 14
+    sizes = [(n, p) for (n, p), _ in windows[0].batches()]
+    assert len(sizes) == 12 and all(idx[p] == 0 and len(idx) == n and len(set(idx)) == n
+                                    for (n, p), idx in windows[0].batches())
+
+
+def test_replay_checks_read_only_selectv_only():
+    """replay's rule: a txn without writes is checked iff it is a selectv txn
+    with a read set; nothing it 'commits' reaches the log."""
+    k = F.enc_int64(1)
+    r = [Range("t", 0, k, k)]
+    w = [(F.REC_UNDO_UPD_DTA, "t", -2, None), (F.REC_UNDO_UPD_IX, "t", 0, k)]
+    seen = []
+
+    def check(log, rs):
+        seen.append((log.nrec, rs.nranges))
+        return model_check(log, rs)[0]
+    for selectv, reads, checked in ((False, r, False), (True, [], False), (True, r, True)):
+        ro, wr = Txn("ro", reads, [], selectv), Txn("w", [], w)
+        ev = [("begin", ro), ("begin", wr), ("commit", wr), ("commit", ro)]
+        del seen[:]
+        rcs = replay(ev, check)
+        assert rcs == ({"w": 0, "ro": 1} if checked else {"w": 0}), (selectv, reads)
+        assert len(seen) == (2 if checked else 1)
+        # the read-only txn passing (snapshot after the write) logs nothing
+        ev = [("begin", wr), ("commit", wr), ("begin", ro), ("commit", ro), ("begin", ro), ("commit", ro)]
+        del seen[:]
+        rcs = replay(ev, check)
+        assert rcs == ({"w": 0, "ro": 0} if checked else {"w": 0})
+        if checked:
+            assert seen[1][0] == seen[2][0] > seen[0][0]             # the log did not grow
 
 
 @pytest.mark.parametrize("seed", range(12))

@@ -40,6 +40,33 @@ def _sequential_run(events, check, e0=1000):
     return txns, rc, seq, snap, cend
 
 
+def test_harness_checks_a_read_only_txn_only_when_it_holds_a_selectv_array():
+    """hsc_harness_commit_protocol's rule for txns without writes, seen on a
+    host-only context, whose full checks fail closed (verdict 1): a selectv txn
+    with a read set gets its one full check (rc 1 here, the check's end
+    recorded), an empty selectv array and a plain read-only txn are never
+    checked (db/sqloffload.c:280-287, 505-524); none of them logs anything."""
+    from comdb2_amd import formats as F
+    from comdb2_amd.hsc import Validator
+    from comdb2_amd.workloads import Txn
+    k = F.enc_int64(1)
+    r = [F.Range("t", 0, k, k)]
+    w = [(F.REC_UNDO_UPD_DTA, "t", -2, None), (F.REC_UNDO_UPD_IX, "t", 0, k)]
+    txns = [Txn("writer", [], w), Txn("selectv", r, [], True), Txn("selectv_empty", [], [], True),
+            Txn("plain", r, [])]
+    events = [("begin", t) for t in txns] + [("commit", t) for t in txns]
+    v = Validator(-1)
+    try:
+        v.ingest_log(F.LogBuilder().build())
+        rc, seq, snap, cend, st = v.commit_protocol(txns, events, 1)
+    finally:
+        v.close()
+    assert rc.tolist() == [0, 1, 0, 0]
+    assert seq.tolist() == [0, -1, -1, -1]
+    assert [int(c) != 0 for c in cend] == [False, True, False, False]
+    assert (st["commits"], st["aborts"], st["full_checks"]) == (1, 1, 1)
+
+
 def test_verifier_accepts_a_sequential_run_and_rejects_a_flip(oracle_mod):
     events = config1_events(n_txn=600)
     check = lambda log, rs: oracle_mod.check(log, rs)[0]

@@ -763,6 +763,8 @@ struct hsc_ctx {
     TallyOut tally_out;
     BankBufs bank;           // hsc_bank_check: device scratch, host results
     BankOut bank_out;
+    PerfBufs perf;           // hsc_perf_check: device scratch and sort rows of its own, host results
+    PerfOut perf_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

@@ -1028,6 +1028,48 @@ struct BankOut {  // host results (hsc_bank_report points into them)
 };
 int bank_group(uint64_t n);  // the lanes a read of the model's n gets: a power of two, at most 64
 hipError_t bank_run(const BankIn &in, BankBufs &b, BankOut &out, hipStream_t s);
+// The perf checker (hsc_perf.hip): a timed history -> the
+// invoke / completion pairs, the latency quantiles per (f, window), the
+// completion counts per (f, type, window).  Its sorts go through t, a set of
+// sort rows of its own, as TallyBufs holds one.
+struct PerfBufs {
+    ResolveBufs t;                               // the sorts' rows and scratch
+    DBuf type, f, proc, client, time;            // the uploaded history
+    DBuf rows, pay;                              // sort rows (stride n) and their payload
+    DBuf comp, inv, lat;                         // per op: completion_of, invoke_of, latency
+    DBuf f0, f1, h0, h1, cpos;                   // per-op flags / scans, cell head flags / scans, cell positions
+    DBuf ct, q;                                  // counters, the quantiles
+    DBuf c_f, c_b, c_n, c_lat;                   // the listed latency cells
+    DBuf r_f, r_t, r_b, r_n;                     // the listed rate cells
+    DBuf goff, raw_op, raw_off;                  // completion group offsets, the raw partition
+    void release_all();
+};
+struct PerfIn {  // host pointers
+    size_t n;
+    const uint8_t *type;
+    const uint32_t *f, *process;
+    const uint8_t *client;
+    const int64_t *time;
+    uint32_t nf, nq;
+    const double *q;
+    double q_dt, r_dt;
+    bool arrays;
+};
+struct PerfOut {  // host results (hsc_perf_report points into them); the vectors are never empty
+    uint64_t invokes, paired, orphans, cells, rate_cells;
+    int64_t t_max;
+    uint32_t cells_listed, rate_listed;
+    std::vector<uint32_t> c_f, c_b, c_n, r_f, r_t, r_b, r_n, raw_op, raw_off;
+    std::vector<int64_t> c_lat, lat;
+    std::vector<uint64_t> counts;
+    std::vector<int32_t> comp, inv;
+    size_t n_arrays, n_raw;
+    int sort_packed;
+    bool bad;  // hipErrorInvalidValue: an f >= nf, a type above info, a negative time or one past the accepted windows
+    float phase_ms[HSC_PERF_NPHASE];
+};
+hipError_t perf_run(const PerfIn &in, PerfBufs &b, PerfOut &out, hipStream_t s);
+hipError_t warm_perf();
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {

@@ -287,6 +287,32 @@ class BankReport(C.Structure):
                 ("negatives", _p), ("n_listed", C.c_uint32), ("listed_read", _p), ("ms", C.c_float)]
 
 
+# hsc_perf_check (include/hip_serial.h)
+PERF_ARRAYS = 1
+PERF_CELL_CAP = 65536
+PERF_MAX_Q, PERF_MAX_F = 64, 65536
+OP_INVOKE, OP_OK, OP_FAIL, OP_INFO = 0, 1, 2, 3
+PERF_PHASES = ("rows", "pair", "cells", "rate", "raw")  # HSC_PERF_MS_ROWS ..
+
+
+class _PerfIn(C.Structure):
+    """hsc_perf_in."""
+    _fields_ = [("n", C.c_size_t), ("type", _p), ("f", _p), ("process", _p), ("client", _p), ("time", _p),
+                ("nf", C.c_uint32), ("nq", C.c_uint32), ("q", _p), ("q_dt", C.c_double), ("r_dt", C.c_double)]
+
+
+class PerfReport(C.Structure):
+    """hsc_perf_report: the arrays are host memory of the context."""
+    _fields_ = [("n", C.c_uint64), ("invokes", C.c_uint64), ("paired", C.c_uint64), ("unpaired", C.c_uint64),
+                ("orphans", C.c_uint64), ("t_max", C.c_int64), ("cells", C.c_uint64), ("rate_cells", C.c_uint64),
+                ("cells_listed", C.c_uint32), ("rate_listed", C.c_uint32),
+                ("cell_f", _p), ("cell_bucket", _p), ("cell_count", _p), ("cell_lat", _p),
+                ("rate_f", _p), ("rate_type", _p), ("rate_bucket", _p), ("rate_count", _p), ("counts", _p),
+                ("n_arrays", C.c_size_t), ("completion_of", _p), ("invoke_of", _p), ("latency", _p),
+                ("n_raw", C.c_size_t), ("raw_op", _p), ("raw_off", _p), ("sort_packed", C.c_int),
+                ("ms", C.c_float), ("phase_ms", C.c_float * len(PERF_PHASES))]
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -367,7 +393,7 @@ EXPORTS = [
     "hsc_dep_graph_resolve", "hsc_dep_graph_build_resolved", "hsc_dep_graph_resolve_sort_path",
     "hsc_dep_graph_resolve_lists", "hsc_dep_graph_build_lists",
     "hsc_dep_graph_internal", "hsc_dep_graph_internal_lists", "hsc_linear_check", "hsc_linear_check_wide",
-    "hsc_tally_check", "hsc_bank_check",
+    "hsc_tally_check", "hsc_bank_check", "hsc_perf_check",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -468,6 +494,7 @@ def load() -> C.CDLL:
         "hsc_linear_check_wide": (C.c_int, [_p, C.POINTER(_LinOps), C.POINTER(_LinWideLimits),
                                             C.POINTER(LinWideReport)]),
         "hsc_tally_check": (C.c_int, [_p, C.POINTER(_TallyIn), C.c_uint, C.POINTER(TallyReport)]),
+        "hsc_perf_check": (C.c_int, [_p, C.POINTER(_PerfIn), C.c_uint, C.POINTER(PerfReport)]),
         "hsc_bank_check": (C.c_int, [_p, C.POINTER(_BankIn), C.POINTER(BankReport)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
@@ -1584,6 +1611,54 @@ class Validator:
         out["found"] = _copy_out(a.found, nr, np.int64)
         out["negatives"] = _copy_out(a.negatives, nr, np.uint32)
         out["listed_read"] = _copy_out(a.listed_read, a.n_listed, np.uint64)
+        return out
+
+    def perf_check(self, type, f, process, client, time, nf: int, qs=(0.5, 0.95, 0.99, 1), q_dt=30, r_dt=10,
+                   arrays: bool = False) -> dict:
+        """The reference's checker/perf over a timed history, one row per op
+        in history order (hsc_perf_check; include/hip_serial.h has the
+        contract): ``type`` OP_INVOKE / OP_OK / OP_FAIL / OP_INFO, ``f`` an id
+        below ``nf``, ``process`` an interned id, ``client`` nonzero when
+        :process is an integer, ``time`` in ns.  ``qs``: the quantiles,
+        ``q_dt`` / ``r_dt``: the quantile and the rate window in seconds.
+        Returns copies of the report: the scalars (``n``, ``invokes``,
+        ``paired``, ``unpaired``, ``orphans``, ``t_max``, ``cells``,
+        ``rate_cells``, ``cells_listed``, ``rate_listed``, ``sort_packed``,
+        ``ms``, ``phase_ms`` by PERF_PHASES, and ``qs``, ``q_dt``, ``r_dt``
+        echoed), the listed latency cells
+        (``cell_f``, ``cell_bucket``, ``cell_count``, ``cell_lat`` [cell, q]),
+        the listed rate cells (``rate_f``, ``rate_type``, ``rate_bucket``,
+        ``rate_count``), ``counts`` [nf, 4], and with ``arrays`` the per-op
+        ``completion_of``, ``invoke_of``, ``latency`` and the raw partition
+        ``raw_op`` / ``raw_off``."""
+        cols = [np.ascontiguousarray(a, t) for a, t in ((type, np.uint8), (f, np.uint32), (process, np.uint32),
+                                                        (client, np.uint8), (time, np.int64))]
+        n = len(cols[0])
+        if any(a.ndim != 1 or len(a) != n for a in cols):
+            raise ValueError("type, f, process, client and time must be 1-d and of one length")
+        q = np.ascontiguousarray(qs, np.float64)
+        if q.ndim != 1:
+            raise ValueError("qs must be 1-d")
+        s = _PerfIn(n, *(a.ctypes.data for a in cols), nf, len(q), q.ctypes.data, q_dt, r_dt)
+        a = PerfReport()
+        self._chk(self.lib.hsc_perf_check(self.ctx, C.byref(s), PERF_ARRAYS if arrays else 0, C.byref(a)),
+                  "hsc_perf_check")
+        out = {k: getattr(a, k) for k in ("n", "invokes", "paired", "unpaired", "orphans", "t_max", "cells",
+                                          "rate_cells", "cells_listed", "rate_listed", "sort_packed", "ms")}
+        out["phase_ms"] = dict(zip(PERF_PHASES, a.phase_ms))
+        out.update(qs=tuple(qs), q_dt=q_dt, r_dt=r_dt)  # (echoed: jepsen.perf_report reads them)
+        for k in ("cell_f", "cell_bucket", "cell_count"):
+            out[k] = _copy_out(getattr(a, k), a.cells_listed, np.uint32)
+        out["cell_lat"] = _copy_out(a.cell_lat, a.cells_listed * len(q), np.int64).reshape(a.cells_listed, len(q))
+        for k in ("rate_f", "rate_type", "rate_bucket", "rate_count"):
+            out[k] = _copy_out(getattr(a, k), a.rate_listed, np.uint32)
+        out["counts"] = _copy_out(a.counts, nf * 4, np.uint64).reshape(nf, 4)
+        if arrays:
+            out["completion_of"] = _copy_out(a.completion_of, a.n_arrays, np.int32)
+            out["invoke_of"] = _copy_out(a.invoke_of, a.n_arrays, np.int32)
+            out["latency"] = _copy_out(a.latency, a.n_arrays, np.int64)
+            out["raw_op"] = _copy_out(a.raw_op, a.n_raw, np.uint32)
+            out["raw_off"] = _copy_out(a.raw_off, nf * 4 + 1, np.uint32)
         return out
 
     def probe_device(self, batch: ProbeBatch) -> None:

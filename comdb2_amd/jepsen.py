@@ -97,10 +97,20 @@ every read's length and total against the model, ``Validator.bank_check``).
 :func:`set_report`, :func:`total_queue_report` and :func:`bank_report` are the
 pure halves; :func:`set_history_edn`, :func:`queue_history_edn` and
 :func:`bank_history_edn` generate histories with known injections.
+
+Every composed checker of core.clj also carries ``:perf (checker/perf)``
+(jepsen/checker.clj:288-309, jepsen/checker/perf.clj): the data sets of the
+latency, latency-quantile and rate graphs.  :func:`check_perf_edn` produces
+them (``Validator.perf_check``; :func:`perf_ops_from_edn` interns the history,
+:func:`perf_report` is the pure half), :func:`with_times` stamps ``:time`` on
+a generated history, and :func:`compose_edn` is ``checker/compose`` with
+``merge-valid`` (:func:`merge_valid`; checker.clj:20-35, :274-286) over the
+checkers of this module.
 """
 from __future__ import annotations
 
 import dataclasses
+import decimal
 import fractions
 import re
 from typing import Dict, List, Optional, Tuple
@@ -1335,6 +1345,290 @@ def check_bank_edn(validator, text: str, n: int, total: int) -> dict:
     test's ``:model`` (accounts, the sum of their starting balances)."""
     ops = bank_ops_from_edn(text)
     return bank_report(ops, validator.bank_check(ops.off, ops.balance, n, total), n, total)
+
+
+# ---------------------------------------------------------------------------
+# checker/perf (latencies, latency quantiles, rates) and checker/compose
+# ---------------------------------------------------------------------------
+PERF_TYPES = (":invoke", ":ok", ":fail", ":info")  # HSC_OP_INVOKE ..
+PERF_GRAPH_TYPES = (":ok", ":info", ":fail")       # perf.clj:158-160, the order the graphs list them in
+PERF_ALL = ":jepsen.checker.perf/all"              # perf.clj's ::all
+_DEC64 = decimal.Context(prec=16, rounding=decimal.ROUND_HALF_EVEN)
+
+
+def _poly_key(v):
+    """A sort key that orders like util/poly-compare (jepsen/util.clj:471-481):
+    ``compare`` inside one class (nil first), the class names across classes."""
+    if v is None:
+        return (0, "", "")
+    if isinstance(v, bool):
+        return (1, "class java.lang.Boolean", v)
+    if isinstance(v, int):
+        return (1, "class java.lang.Long", v)
+    if isinstance(v, str):
+        return (1, "class clojure.lang.Keyword" if v.startswith(":") else "class java.lang.String", v)
+    raise ValueError(f"an :f the perf checker cannot order: {v!r}")
+
+
+def nanos_to_ms(ns: int) -> float:
+    """``(double (util/nanos->ms ns))`` (jepsen/util.clj:216, perf.clj:134): the
+    ratio ns / 1000000 as a double.  Clojure converts a ratio through 16
+    decimal digits (``Ratio.doubleValue``), which is the correctly rounded
+    quotient for every |ns| below 10^16."""
+    ns = int(ns)
+    if abs(ns) < 10 ** 16 or ns % 1000000 == 0:
+        return ns / 1000000
+    return float(_DEC64.divide(decimal.Decimal(ns), decimal.Decimal(1000000)))
+
+
+def bucket_of(t_ns: int, dt) -> int:
+    """The window of a time under ``dt`` seconds: perf.clj:15-25 after
+    util/nanos->secs, two double divisions, truncated."""
+    return int((int(t_ns) / 1e9) / dt)
+
+
+def bucket_mid(b: int, dt):
+    """bucket-scale (perf.clj:15-19): the window's midpoint in seconds."""
+    return b * dt + dt / 2
+
+
+@dataclasses.dataclass
+class PerfOps:
+    """A timed history as ``Validator.perf_check`` takes it: one row per op in
+    history order.  ``fs`` / ``processes``: what the ``f`` / ``process`` ids
+    stand for (``fs`` in util/polysort order); ``nemesis``: the (:f, time) of
+    the ``:process :nemesis`` ops in history order."""
+    type: np.ndarray
+    f: np.ndarray
+    process: np.ndarray
+    client: np.ndarray
+    time: np.ndarray
+    fs: List
+    processes: List
+    nemesis: List[Tuple[object, int]]
+
+
+def perf_ops_from_edn(text: str) -> PerfOps:
+    """Interns ``:f`` and ``:process`` of every op map.  Raises ValueError for
+    an op without an integer ``:time`` (the reference throws there too: a
+    NullPointerException in util/history->latencies) or a ``:type`` that is
+    none of PERF_TYPES."""
+    rows = []
+    for i, op in enumerate(o for o in _flatten(parse_edn(text)) if isinstance(o, dict)):
+        t = op.get(":time")
+        if type(t) is not int or not 0 <= t < (1 << 63):
+            raise ValueError(f"op {i}: no integer :time in [0, 2^63): {t!r}")
+        if op.get(":type") not in PERF_TYPES:
+            raise ValueError(f"op {i}: :type {op.get(':type')!r}")
+        p = op.get(":process")
+        if isinstance(p, (list, dict)):
+            raise ValueError(f"op {i}: :process {p!r}")
+        rows.append((PERF_TYPES.index(op[":type"]), op.get(":f"), p, t))
+    fs = sorted({r[1] for r in rows}, key=_poly_key)
+    fid = {v: k for k, v in enumerate(fs)}
+    pid: Dict[object, int] = {}
+    for r in rows:
+        pid.setdefault((type(r[2]), r[2]), len(pid))
+    n = len(rows)
+    return PerfOps(np.fromiter((r[0] for r in rows), np.uint8, n), np.fromiter((fid[r[1]] for r in rows), np.uint32, n),
+                   np.fromiter((pid[(type(r[2]), r[2])] for r in rows), np.uint32, n),
+                   np.fromiter((type(r[2]) is int for r in rows), np.uint8, n),
+                   np.fromiter((r[3] for r in rows), np.int64, n), fs, [k[1] for k in pid],
+                   [(r[1], r[3]) for r in rows if r[2] == ":nemesis"])
+
+
+def nemesis_intervals(nemesis, last_time: Optional[int]) -> List[Tuple[float, float]]:
+    """perf.clj:168-187 over util/nemesis-intervals (jepsen/util.clj:589-606):
+    ``nemesis`` = the (:f, time ns) of the nemesis ops in history order.  A
+    ``:stop`` closes the oldest open ``:start`` (a queue: start start stop stop
+    pairs first with third, second with fourth); a stop with no start open is
+    dropped; a start never stopped ends at ``last_time``, the history's last
+    time.  [(start s, stop s), ...]: the closed ones in stop order, then the
+    open ones."""
+    pairs, starts = [], []
+    for f, t in nemesis:
+        if f == ":start":
+            starts.append(t)
+        elif f == ":stop":
+            pairs.append((starts.pop(0) if starts else None, t))
+    pairs += [(t, None) for t in starts]
+    return [(a / 1e9, (last_time if b is None else b) / 1e9) for a, b in pairs if a is not None]
+
+
+def perf_report(ops: PerfOps, res: dict) -> dict:
+    """checker/perf's data sets from a ``Validator.perf_check`` dict of ``ops``
+    (a pure function of its arguments; the windows and quantiles are the
+    ``q_dt``, ``r_dt`` and ``qs`` the dict echoes):
+
+    ``valid``: True (checker.clj:295, :303).  ``latency_raw`` (only when the
+    dict has the arrays): {f: {":ok" | ":info" | ":fail": [(seconds, ms), ...]}}
+    in history order, for every f with an invoke (perf.clj:96-102, :129-134).
+    ``latency_quantiles``: {f: {q: [(window midpoint s, ms), ...]}} by window
+    (perf.clj:45-79, :246-260).  ``rate``: {f: {type: [(midpoint, hz), ...]}}
+    as rate-graph! emits it (perf.clj:293-331): for every f with a client
+    completion and each of PERF_GRAPH_TYPES the series over the midpoints <=
+    t-max, 0 where no op fell, a value being 1/dt added once per op (not count
+    / dt); a completion in a last, partly filled window whose midpoint lies
+    past t-max is therefore not in the series.  ``counts``: perf.clj:113-127's
+    map {f: {type: n, PERF_ALL: n}, PERF_ALL: {...}} over every op that is no
+    invoke.  ``nemesis_intervals``: :func:`nemesis_intervals`.  The scalars
+    ``n``, ``invokes``, ``paired``, ``unpaired``, ``orphans``, ``t_max``,
+    ``cells``, ``rate_cells``; ``truncated``: the data sets ("latency_quantiles",
+    "rate") with more cells than the entry lists; ``perf``: the entry's dict.
+
+    Unpaired invokes -- an invoke whose process invoked again first, or that
+    never completed: the reference cannot plot a history with one
+    (latency-point divides nil).  Here they are left out of every data set and
+    counted in ``unpaired``."""
+    qs, q_dt, r_dt = list(res["qs"]), res["q_dt"], res["r_dt"]
+    fs = ops.fs
+    invoked = np.bincount(ops.f[ops.type == 0], minlength=len(fs)) if len(ops.f) else np.zeros(len(fs), np.int64)
+    report = {"valid": True}
+    if "raw_op" in res:
+        raw = {}
+        off = res["raw_off"]
+        for k, f in enumerate(fs):
+            if not invoked[k]:
+                continue
+            raw[f] = {}
+            for t in PERF_GRAPH_TYPES:
+                g = k * 4 + PERF_TYPES.index(t)
+                idx = res["raw_op"][int(off[g]):int(off[g + 1])]
+                raw[f][t] = [(int(ops.time[i]) / 1e9, nanos_to_ms(res["latency"][i])) for i in idx]
+        report["latency_raw"] = raw
+    quant = {f: {q: [] for q in qs} for k, f in enumerate(fs) if invoked[k]}
+    for k in range(int(res["cells_listed"])):
+        f = fs[int(res["cell_f"][k])]
+        mid = bucket_mid(int(res["cell_bucket"][k]), q_dt)
+        for j, q in enumerate(qs):
+            quant[f][q].append((mid, nanos_to_ms(res["cell_lat"][k][j])))
+    report["latency_quantiles"] = quant
+    # rate: 1 / dt added count times, sequentially, as the reduce of perf.clj:304-311 does
+    td = 1.0 / r_dt  # (double (/ dt)), perf.clj:297
+    most = int(res["rate_count"].max()) if len(res["rate_count"]) else 0
+    hz = np.concatenate([[0.0], np.cumsum(np.full(most, td))])  # (numpy's cumsum adds in order)
+    t_max = int(res["t_max"]) / 1e9
+    mids = []
+    while bucket_mid(len(mids), r_dt) <= t_max:
+        mids.append(bucket_mid(len(mids), r_dt))
+    rate = {}
+    for f_, t_, b_, c_ in zip(res["rate_f"], res["rate_type"], res["rate_bucket"], res["rate_count"]):
+        if fs[int(f_)] not in rate:
+            rate[fs[int(f_)]] = {t: [0] * len(mids) for t in PERF_GRAPH_TYPES}
+        series = rate[fs[int(f_)]]
+        if int(b_) < len(mids):
+            series[PERF_TYPES[int(t_)]][int(b_)] = float(hz[int(c_)])
+    report["rate"] = {f: {t: list(zip(mids, v)) for t, v in d.items()} for f, d in rate.items()}
+    counts: Dict = {}
+    for k, f in enumerate(fs):
+        for t in (1, 2, 3):
+            c = int(res["counts"][k][t])
+            if c:
+                for a, b in ((f, PERF_TYPES[t]), (f, PERF_ALL), (PERF_ALL, PERF_TYPES[t]), (PERF_ALL, PERF_ALL)):
+                    counts.setdefault(a, {})
+                    counts[a][b] = counts[a].get(b, 0) + c
+    report["counts"] = counts
+    report["nemesis_intervals"] = nemesis_intervals(ops.nemesis, int(ops.time[-1]) if len(ops.time) else None)
+    for k in ("n", "invokes", "paired", "unpaired", "orphans", "t_max", "cells", "rate_cells"):
+        report[k] = int(res[k])
+    report["truncated"] = [name for name, a, b in (("latency_quantiles", "cells", "cells_listed"),
+                                                   ("rate", "rate_cells", "rate_listed")) if res[a] > res[b]]
+    report["perf"] = res
+    return report
+
+
+def check_perf_edn(validator, text: str, arrays: bool = False, **windows) -> dict:
+    """checker/perf through the GPU: :func:`perf_ops_from_edn`,
+    ``Validator.perf_check``, :func:`perf_report`.  ``windows``: ``qs``,
+    ``q_dt``, ``r_dt`` of ``perf_check``; ``arrays``: also ``latency_raw``."""
+    ops = perf_ops_from_edn(text)
+    res = validator.perf_check(ops.type, ops.f, ops.process, ops.client, ops.time, max(len(ops.fs), 1),
+                               arrays=arrays, **windows)
+    return perf_report(ops, res)
+
+
+def with_times(text: str, seed: int, mean_latency_ns: int = 1_000_000, nemesis=()) -> str:
+    """The EDN history ``text`` (one op map per line, as the generators here
+    write them, which carry no ``:time``) with strictly increasing integer
+    ``:time`` s stamped on its lines: the gaps are 1 + exponential with mean
+    ``mean_latency_ns`` divided by the number of processes seen, so that an
+    op's latency comes to about ``mean_latency_ns``.  ``nemesis``: (line, "start"
+    | "stop") pairs; before that line of ``text`` the nemesis's two ``:info``
+    ops of that ``:f`` are spliced in, as Jepsen logs a nemesis action."""
+    rng = np.random.default_rng(seed)
+    lines = [ln for ln in text.split("\n") if ln.strip()]
+    procs = len(set(re.findall(r":process (\S+?)[,}]", text))) or 1
+    splice: Dict[int, List[str]] = {}
+    for at, what in nemesis:
+        if what not in ("start", "stop"):
+            raise ValueError(f"nemesis: {what!r}")
+        splice.setdefault(min(max(int(at), 0), len(lines)), []).extend(
+            [f"{{:type :info, :f :{what}, :process :nemesis, :value nil}}"] * 2)
+    out, t = [], 0
+    for i in range(len(lines) + 1):
+        for ln in splice.get(i, []) + (lines[i:i + 1]):
+            ln = ln.rstrip()
+            if not ln.endswith("}"):
+                raise ValueError(f"line {i}: not one op map per line")
+            t += 1 + int(rng.exponential(mean_latency_ns / procs))
+            out.append(f"{ln[:-1]}, :time {t}}}")
+    return "\n".join(out) + "\n"
+
+
+_VALID_PRIORITIES = ((True, 0), ("unknown", 0.5), (False, 1))  # checker.clj:20-25
+
+
+def merge_valid(valids):
+    """merge-valid (checker.clj:27-35): of True, "unknown" and False the one of
+    the highest priority (True 0, "unknown" 0.5, False 1).  Raises ValueError
+    for no values or a value that is none of the three."""
+    def priority(v):
+        for name, p in _VALID_PRIORITIES:
+            if v is name or (isinstance(v, str) and v == name):
+                return p
+        raise ValueError(f"not a :valid? value: {v!r}")
+    valids = list(valids)
+    if not valids:
+        raise ValueError("merge_valid of nothing")
+    best = valids[0]
+    priority(best)
+    for v in valids[1:]:
+        if priority(best) < priority(v):
+            best = v
+    return best
+
+
+def compose_edn(validator, text: str, checkers: dict) -> dict:
+    """checker/compose (checker.clj:274-286): runs every ``checkers[name]
+    (validator, text)`` on the history and returns {name: its report, ...,
+    "valid": :func:`merge_valid` of the reports' ``valid``}.  A member that
+    raises gives {"valid": "unknown", "error": the exception's text}, as
+    check-safe does (checker.clj:54-64).  A key that
+    :func:`check_linear_edn` leaves undecided makes its report, and so the
+    composition unless another member is invalid, "unknown".
+
+    The presets are the compositions of core.clj whose members exist
+    unambiguously here: COMPOSE_SETS (:269-271), COMPOSE_REGISTER (:585-587,
+    :610-612) and :func:`compose_bank` (:291-294, :313-316).  core.clj also
+    lists an ``independent`` linearizable member for its bank and dirty-reads
+    tests; the presets leave it out, a caller may add it."""
+    results = {}
+    for name, check in checkers.items():
+        try:
+            results[name] = check(validator, text)
+        except Exception as e:  # noqa: BLE001  (check-safe catches Throwable)
+            results[name] = {"valid": "unknown", "error": f"{type(e).__name__}: {e}"}
+    results["valid"] = merge_valid(r["valid"] for r in list(results.values()))
+    return results
+
+
+COMPOSE_SETS = {"perf": check_perf_edn, "set": check_set_edn}
+COMPOSE_REGISTER = {"perf": check_perf_edn, "linearizable": check_linear_edn}
+
+
+def compose_bank(n: int, total: int) -> dict:
+    """The bank tests' composition for the model (n accounts, total)."""
+    return {"perf": check_perf_edn, "bank": lambda v, text: check_bank_edn(v, text, n, total)}
 
 
 # ---------------------------------------------------------------------------

@@ -1434,6 +1434,95 @@ typedef struct hsc_bank_report {
     float ms;                      /* device time of the whole call */
 } hsc_bank_report;
 int hsc_bank_check(hsc_ctx *ctx, const hsc_bank_in *in, hsc_bank_report *out);
+
+/* ---- the perf checker: latencies, latency quantiles, completion rates --------
+ * checker/perf (jepsen/checker.clj:288-309), the member every composed checker
+ * of core.clj carries beside its workload's own: the data sets of the three
+ * graphs of jepsen/checker/perf.clj and its rate breakdown.  DESIGN.md §5l.
+ * The history is one row per op in history order: type (HSC_OP_INVOKE / _OK /
+ * _FAIL / _INFO), f (an id below nf), process (an id: the host interns any
+ * value, an integer or :nemesis alike), client (nonzero when :process is an
+ * integer -- the rate graph's (comp integer? :process), perf.clj:302) and time
+ * in ns.
+ * Pairing is util/history->latencies (jepsen/util.clj:553-587): an invoke
+ * becomes its process's outstanding invoke (replacing an older one), any other
+ * op pairs with its process's outstanding invoke and removes it.  Per op:
+ * completion_of (the op that completed this invoke, else -1), invoke_of (the
+ * invoke this op completed, else -1), latency (ns, signed and never clamped:
+ * time[completion] - time[invoke]; 0 where completion_of is -1).  invokes =
+ * paired + unpaired; orphans: the ops that are no invoke and completed none.
+ * Windows: time t lies in window (long)(((double)t / 1e9) / dt), the
+ * reference's two double divisions (perf.clj:15-25, :129-134, :307-309),
+ * computed so on the device.  Accepted are the times whose window index is
+ * below 2^32 under both q_dt and r_dt -- every int64 time when both windows are
+ * at least 2.15 s -- a time past that is HSC_EINVAL.
+ * Latency cells: the paired invokes by (f, window of the invoke's time under
+ * q_dt).  cells is exact; the first cells_listed = min(cells,
+ * HSC_PERF_CELL_CAP) are listed in (f, window) order with their count and, per
+ * q[j], the latency at index min(count - 1, (long)floor(count * q[j])) of the
+ * cell's ascending latencies (perf.clj:45-55): cell_lat[k * nq + j].
+ * Rate cells: the ops that are no invoke and have client set, by (f, type,
+ * window of their time under r_dt), listed like the latency cells (rate_cells
+ * exact, rate_listed).  counts[f * 4 + type]: the ops of that f and type that
+ * are no invoke, whatever client says (perf.clj:113-127; its ::all margins are
+ * sums over this matrix).  t_max: the largest time, 0 for an empty history.
+ * With HSC_PERF_ARRAYS also the raw partition (perf.clj:96-102): raw_op holds
+ * the paired invokes grouped by g = f * 4 + type of their completion, history
+ * order inside a group, group g at raw_op[raw_off[g] .. raw_off[g + 1]);
+ * without it completion_of / invoke_of / latency / raw_op are empty and
+ * raw_off is all zero.
+ * HSC_PERF_CELL_CAP: a test of 8 :f values fills 65536 rate cells (three
+ * completion types, 10 s windows) after 7.5 hours and as many latency cells
+ * (30 s windows) after 68 hours; the suite's tests run minutes.  A longer
+ * history still gets every exact scalar and the first cells.
+ * HSC_EINVAL: a NULL argument (an array may be NULL when n is 0, q when nq is
+ * 0), nf of 0 or above 65536, an f >= nf, a type above HSC_OP_INFO, a negative
+ * time or one past the accepted windows, a q outside [0, 1] or NaN, nq above
+ * 64, a window that is not a finite number above 0, a flag other than
+ * HSC_PERF_ARRAYS, or n > 0x7FFFFFFF (every position is scanned as a u32).
+ * HSC_EDEVICE: a host-only context.  An empty history succeeds with empty
+ * outputs.  The arrays are host memory owned by the context, never NULL, valid
+ * until the next hsc_perf_check on it.  Nothing a resolve, a build, a tally or
+ * a linear check left on the context is touched: the sorts have rows of their
+ * own. */
+#define HSC_PERF_ARRAYS 1u
+#define HSC_PERF_CELL_CAP 65536
+#define HSC_PERF_MAX_Q 64
+#define HSC_PERF_MAX_F 65536
+enum { HSC_OP_INVOKE, HSC_OP_OK, HSC_OP_FAIL, HSC_OP_INFO };
+enum { HSC_PERF_MS_ROWS, HSC_PERF_MS_PAIR, HSC_PERF_MS_CELLS, HSC_PERF_MS_RATE, HSC_PERF_MS_RAW, HSC_PERF_NPHASE };
+typedef struct hsc_perf_in {
+    size_t n;
+    const uint8_t *type;           /* [n] */
+    const uint32_t *f;             /* [n] below nf */
+    const uint32_t *process;       /* [n] */
+    const uint8_t *client;         /* [n] */
+    const int64_t *time;           /* [n] ns, >= 0 */
+    uint32_t nf;
+    uint32_t nq;
+    const double *q;               /* [nq] in [0, 1] */
+    double q_dt, r_dt;             /* the quantile and the rate window, seconds */
+} hsc_perf_in;
+typedef struct hsc_perf_report {
+    uint64_t n, invokes, paired, unpaired, orphans;
+    int64_t t_max;
+    uint64_t cells, rate_cells;
+    uint32_t cells_listed, rate_listed;
+    const uint32_t *cell_f, *cell_bucket, *cell_count;    /* [cells_listed] */
+    const int64_t *cell_lat;                              /* [cells_listed * nq] */
+    const uint32_t *rate_f, *rate_type, *rate_bucket, *rate_count;  /* [rate_listed] */
+    const uint64_t *counts;                               /* [nf * 4] */
+    size_t n_arrays;                                      /* n with HSC_PERF_ARRAYS, else 0 */
+    const int32_t *completion_of, *invoke_of;             /* [n_arrays] */
+    const int64_t *latency;                               /* [n_arrays] */
+    size_t n_raw;                                         /* paired with HSC_PERF_ARRAYS, else 0 */
+    const uint32_t *raw_op;                               /* [n_raw] */
+    const uint32_t *raw_off;                              /* [nf * 4 + 1] */
+    int sort_packed;               /* bit 0: the process sort ran as packed single words, 1: the latency cells', 2: the rate cells', 3: the raw partition's */
+    float ms;                      /* device time of the whole call */
+    float phase_ms[HSC_PERF_NPHASE]; /* of it: upload + rows, pairing, latency cells, rate, raw partition */
+} hsc_perf_report;
+int hsc_perf_check(hsc_ctx *ctx, const hsc_perf_in *in, unsigned flags, hsc_perf_report *out);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst

@@ -765,6 +765,9 @@ struct hsc_ctx {
     BankOut bank_out;
     PerfBufs perf;           // hsc_perf_check: device scratch and sort rows of its own, host results
     PerfOut perf_out;
+    CountBufs count;         // hsc_counter_check / hsc_queue_check: device scratch and sort rows of their own, host results
+    CounterOut counter_out;
+    QueueOut queue_out;
 
     // Probe lanes: the probe scratch above belongs to the active lane; other
     // lanes park theirs here.  A lane is bound to the stream that last used

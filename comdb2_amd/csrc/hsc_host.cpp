@@ -2777,7 +2777,7 @@ int hsc_ctx_create(int device, hsc_ctx **out)
         if (!warmed[device]) {
             for (auto f : {warm_kernels, warm_ingest, warm_narrow, warm_ctiles, warm_delta,
                            warm_compact, warm_csort, warm_coalesce, warm_edges, warm_graph, warm_realtime, warm_anomaly, warm_si,
-                           warm_resolve, warm_lists, warm_internal, warm_linear, warm_linear_wide, warm_tally, warm_perf, warm_route})
+                           warm_resolve, warm_lists, warm_internal, warm_linear, warm_linear_wide, warm_tally, warm_perf, warm_count, warm_route})
                 (void)f();
             warmed[device] = true;
         }
@@ -2860,6 +2860,7 @@ void hsc_ctx_destroy(hsc_ctx *c)
     c->tally.release_all();
     c->bank.release_all();
     c->perf.release_all();
+    c->count.release_all();
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);

@@ -206,7 +206,7 @@ hipError_t packed_sort_dedupe(const PackPlan &P, size_t n, const uint32_t *gid, 
 // LSNs, no index -- also each distinct writer's ww row, decoded by ww_pp)
 // (err != null: the one-sweep passes -- no count pass or scan per digit --
 // with *err set if a tile's look-back stalled; the caller fails the build)
-size_t scan_scratch_bytes(size_t n);
+size_t scan_scratch_bytes(size_t n, size_t elem = sizeof(uint32_t));  // elem: bytes of a scanned element
 // (src != null: the tile-max sparse table derived from one over the same rows'
 // LSNs with tiles 2^shift times shorter (shift 0 or 1, at least as many
 // levels) instead of rebuilt -- the narrow tile view's, whose LSNs are the
@@ -1070,6 +1070,58 @@ struct PerfOut {  // host results (hsc_perf_report points into them); the vector
 };
 hipError_t perf_run(const PerfIn &in, PerfBufs &b, PerfOut &out, hipStream_t s);
 hipError_t warm_perf();
+// The counter and queue checkers (hsc_count.hip), per
+// independent key.  Their sorts go through t, a set of sort rows of their own,
+// as TallyBufs and PerfBufs hold one; the two entries share the buffers (one
+// runs at a time under the context's lock) and keep host results of their own.
+struct CountBufs {
+    ResolveBufs t;                               // the sorts' rows and scratch
+    DBuf type, f, proc, value, key;              // the uploaded rows
+    DBuf rows, pay;                              // sort rows (stride n) and their payload
+    DBuf inv, eff, malk;                         // counter, per op: invoke_of, effective value, malformed kind
+    DBuf ord, posof;                             // key order: the row at a position, a row's position
+    DBuf a0, a1, s64;                            // the u64 scans (upper / lower; queue: enqueue values) and their scratch
+    DBuf f0, f1, f2, rpos;                       // u32 flags / scans, run head positions
+    DBuf khead, kmin, ct;                        // per key: first position, minimum (index << 3 | kind); counters
+    DBuf k_verdict, k_op, k_kind, k_u0, k_off;   // per key outputs
+    DBuf r_lo, r_val, r_hi, r_op, r_list;        // per read / per final element outputs
+    void release_all();
+};
+struct CounterIn {  // host pointers (checked by the caller)
+    size_t n;
+    const uint8_t *type, *f;
+    const uint32_t *process;
+    const int64_t *value;
+    const uint32_t *key;  // null: every row has key 0
+    uint32_t nkeys;
+};
+struct CounterOut {  // host results (hsc_counter_report points into them); the vectors are never empty
+    std::vector<uint8_t> verdict, mal_kind;
+    std::vector<uint32_t> mal_op, read_off, read_op, errors, listed;
+    std::vector<int64_t> lower, value, upper;
+    uint64_t reads, bad_reads;
+    uint32_t n_listed, bad, unknown;
+    int sort_packed;
+};
+hipError_t counter_run(const CounterIn &in, CountBufs &b, CounterOut &out, hipStream_t s);
+struct QueueIn {  // host pointers (checked by the caller)
+    size_t n;
+    const uint8_t *f;
+    const int64_t *value;
+    const uint32_t *key;  // null: every row has key 0
+    uint32_t nkeys;
+    bool fifo, final;
+};
+struct QueueOut {  // host results (hsc_queue_report points into them); the vectors are never empty
+    std::vector<uint8_t> verdict, kind;
+    std::vector<uint32_t> error_row, final_len, final_off, final_mult;
+    std::vector<int64_t> final_val;
+    uint64_t n_final;
+    uint32_t bad;
+    int sort_packed;
+};
+hipError_t queue_run(const QueueIn &in, CountBufs &b, QueueOut &out, hipStream_t s);
+hipError_t warm_count();
 // Compact codes of wide windows (hsc_compact.hip): per group the key bits
 // that vary between its rows, most significant first, in WC words.
 struct CompactTables {
@@ -1190,6 +1242,9 @@ hipError_t graph_scc_rows(uint32_t nn, const uint8_t *cover, const uint64_t *row
 hipError_t swap_edge_words(uint32_t m, const uint32_t *src, const uint32_t *dst, uint64_t *rows,
                            hipStream_t s);
 hipError_t scan_exclusive_u32(uint32_t *a, size_t n, uint32_t *scratch, hipStream_t s);
+// The same scan over u64 (sums wrap, so one instance serves int64 too);
+// scratch >= scan_scratch_bytes(n, 8) bytes
+hipError_t scan_exclusive_u64(uint64_t *a, size_t n, uint64_t *scratch, hipStream_t s);
 
 // Raw log decoder (hsc_logdec.cpp): bytes -> the hsc_llog SoA it owns.
 struct DecodedLog {

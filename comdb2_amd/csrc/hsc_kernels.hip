@@ -360,24 +360,37 @@ __global__ __launch_bounds__(kSortThreads) void k_rs_scatter(
     }
 }
 
-// ---- generic exclusive scan of u32 (in place), block sums recursively -----
+// ---- generic exclusive scan (in place), block sums recursively -------------
+// T = uint32_t or uint64_t; sums wrap.  Three kernels per level and no
+// workgroup ever waits on another: tile scan with block sums, the same scan of
+// the sums, an add pass.
 constexpr int kScanThreads = 256;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kScanThreads * kScanItems;
 
-__global__ __launch_bounds__(kScanThreads) void k_scan_tile(uint32_t *a, size_t n, uint32_t *sums)
+__device__ __forceinline__ uint32_t scan_block(uint32_t v, uint32_t *lds, uint32_t &total)
 {
-    __shared__ uint32_t lds[kScanThreads / 64];
+    return block_excl_scan<kScanThreads>(v, lds, total);
+}
+__device__ __forceinline__ uint64_t scan_block(uint64_t v, uint64_t *lds, uint64_t &total)
+{
+    return block_excl_scan64<kScanThreads>(v, lds, total);
+}
+
+template <class T>
+__global__ __launch_bounds__(kScanThreads) void k_scan_tile(T *a, size_t n, T *sums)
+{
+    __shared__ T lds[kScanThreads / 64];
     const size_t base = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanItems;
-    uint32_t v[kScanItems];
-    uint32_t s = 0;
+    T v[kScanItems];
+    T s = 0;
 #pragma unroll
     for (int k = 0; k < kScanItems; ++k) {
         v[k] = (base + k < n) ? a[base + k] : 0;
         s += v[k];
     }
-    uint32_t total;
-    uint32_t pre = block_excl_scan<kScanThreads>(s, lds, total);
+    T total;
+    T pre = scan_block(s, lds, total);
 #pragma unroll
     for (int k = 0; k < kScanItems; ++k) {
         if (base + k < n) a[base + k] = pre;
@@ -386,43 +399,55 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_tile(uint32_t *a, size_t 
     if (threadIdx.x == 0 && sums) sums[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(kScanThreads) void k_scan_add(uint32_t *a, size_t n, const uint32_t *sums)
+template <class T>
+__global__ __launch_bounds__(kScanThreads) void k_scan_add(T *a, size_t n, const T *sums)
 {
-    const uint32_t add = sums[blockIdx.x];
+    const T add = sums[blockIdx.x];
     const size_t base = (size_t)blockIdx.x * kScanTile;
     for (int k = threadIdx.x; k < kScanTile; k += kScanThreads)
         if (base + k < n) a[base + k] += add;
 }
 
-size_t scan_scratch_bytes(size_t n)
+size_t scan_scratch_bytes(size_t n, size_t elem)
 {
     size_t total = 0;
     while (n > (size_t)kScanTile) {
         n = (n + kScanTile - 1) / kScanTile;
-        total += n * sizeof(uint32_t);
+        total += n * elem;
     }
     return total + 256;
 }
 
-static hipError_t scan_u32(uint32_t *a, size_t n, uint32_t *scratch, hipStream_t s)
+template <class T>
+static hipError_t scan_rec(T *a, size_t n, T *scratch, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
     size_t nb = (n + kScanTile - 1) / kScanTile;
     if (nb == 1) {
-        k_scan_tile<<<1, kScanThreads, 0, s>>>(a, n, nullptr);
+        k_scan_tile<T><<<1, kScanThreads, 0, s>>>(a, n, nullptr);
         return hipGetLastError();
     }
-    uint32_t *sums = scratch;
-    k_scan_tile<<<(unsigned)nb, kScanThreads, 0, s>>>(a, n, sums);
-    hipError_t e = scan_u32(sums, nb, scratch + nb, s);
+    T *sums = scratch;
+    k_scan_tile<T><<<(unsigned)nb, kScanThreads, 0, s>>>(a, n, sums);
+    hipError_t e = scan_rec<T>(sums, nb, scratch + nb, s);
     if (e != hipSuccess) return e;
-    k_scan_add<<<(unsigned)nb, kScanThreads, 0, s>>>(a, n, sums);
+    k_scan_add<T><<<(unsigned)nb, kScanThreads, 0, s>>>(a, n, sums);
     return hipGetLastError();
+}
+
+static hipError_t scan_u32(uint32_t *a, size_t n, uint32_t *scratch, hipStream_t s)
+{
+    return scan_rec<uint32_t>(a, n, scratch, s);
 }
 
 hipError_t scan_exclusive_u32(uint32_t *a, size_t n, uint32_t *scratch, hipStream_t s)
 {
     return scan_u32(a, n, scratch, s);
+}
+
+hipError_t scan_exclusive_u64(uint64_t *a, size_t n, uint64_t *scratch, hipStream_t s)
+{
+    return scan_rec<uint64_t>(a, n, scratch, s);
 }
 
 size_t radix_scratch_bytes(size_t n, int W)

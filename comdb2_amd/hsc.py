@@ -313,6 +313,43 @@ class PerfReport(C.Structure):
                 ("ms", C.c_float), ("phase_ms", C.c_float * len(PERF_PHASES))]
 
 
+# hsc_counter_check / hsc_queue_check (include/hip_serial.h)
+COUNTER_LIST_CAP = 4096
+CNT_NIL = -(1 << 63)
+CNT_ADD, CNT_READ, CNT_OTHER = 0, 1, 2
+CNT_OK, CNT_BAD, CNT_UNKNOWN = 0, 1, 2  # a key's verdict, both entries
+QUEUE_FIFO, QUEUE_FINAL = 1, 2
+Q_ENQUEUE, Q_DEQUEUE = 0, 1
+NO_ROW = 0xFFFFFFFF  # malformed_op / error_row: none
+
+
+class _CounterIn(C.Structure):
+    """hsc_counter_in."""
+    _fields_ = [("n", C.c_size_t), ("type", _p), ("f", _p), ("process", _p), ("value", _p), ("key", _p),
+                ("nkeys", C.c_uint32)]
+
+
+class CounterReport(C.Structure):
+    """hsc_counter_report: the arrays are host memory of the context."""
+    _fields_ = [("nkeys", C.c_uint32), ("bad", C.c_uint32), ("unknown", C.c_uint32), ("verdict", _p),
+                ("malformed_op", _p), ("malformed_kind", _p), ("read_off", _p), ("reads", C.c_uint64),
+                ("bad_reads", C.c_uint64), ("lower", _p), ("value", _p), ("upper", _p), ("read_op", _p),
+                ("errors", _p), ("n_listed", C.c_uint32), ("listed_read", _p), ("sort_packed", C.c_int),
+                ("ms", C.c_float)]
+
+
+class _QueueIn(C.Structure):
+    """hsc_queue_in."""
+    _fields_ = [("n", C.c_size_t), ("f", _p), ("value", _p), ("key", _p), ("nkeys", C.c_uint32)]
+
+
+class QueueReport(C.Structure):
+    """hsc_queue_report: the arrays are host memory of the context."""
+    _fields_ = [("nkeys", C.c_uint32), ("bad", C.c_uint32), ("verdict", _p), ("error_row", _p), ("error_kind", _p),
+                ("final_len", _p), ("final_off", _p), ("n_final", C.c_uint64), ("final_val", _p),
+                ("final_mult", _p), ("sort_packed", C.c_int), ("ms", C.c_float)]
+
+
 class OpsDev(C.Structure):
     """hsc_ops_dev: one key shard's history ops on its member's GPU."""
     _fields_ = [("nops", C.c_size_t), ("txn", _p), ("key", _p), ("is_write", _p), ("observed", _p)]
@@ -393,7 +430,7 @@ EXPORTS = [
     "hsc_dep_graph_resolve", "hsc_dep_graph_build_resolved", "hsc_dep_graph_resolve_sort_path",
     "hsc_dep_graph_resolve_lists", "hsc_dep_graph_build_lists",
     "hsc_dep_graph_internal", "hsc_dep_graph_internal_lists", "hsc_linear_check", "hsc_linear_check_wide",
-    "hsc_tally_check", "hsc_bank_check", "hsc_perf_check",
+    "hsc_tally_check", "hsc_bank_check", "hsc_perf_check", "hsc_counter_check", "hsc_queue_check",
     "hsc_multi_create", "hsc_multi_unique_ids", "hsc_multi_create_rank", "hsc_multi_world",
     "hsc_multi_rank", "hsc_multi_local", "hsc_multi_member", "hsc_multi_set_splitters",
     "hsc_multi_adopt", "hsc_multi_probe_device", "hsc_multi_stats", "hsc_multi_last_counts",
@@ -496,6 +533,8 @@ def load() -> C.CDLL:
         "hsc_tally_check": (C.c_int, [_p, C.POINTER(_TallyIn), C.c_uint, C.POINTER(TallyReport)]),
         "hsc_perf_check": (C.c_int, [_p, C.POINTER(_PerfIn), C.c_uint, C.POINTER(PerfReport)]),
         "hsc_bank_check": (C.c_int, [_p, C.POINTER(_BankIn), C.POINTER(BankReport)]),
+        "hsc_counter_check": (C.c_int, [_p, C.POINTER(_CounterIn), C.POINTER(CounterReport)]),
+        "hsc_queue_check": (C.c_int, [_p, C.POINTER(_QueueIn), C.c_uint, C.POINTER(QueueReport)]),
         "hsc_dep_graph_scc_cut": (C.c_int, [_p, C.c_uint32, _p, _p, C.c_size_t, _p,
                                             C.POINTER(GraphStats)]),
         "hsc_window_ingest_raw": (C.c_int, [_p, C.POINTER(_RawLog)]),
@@ -1659,6 +1698,77 @@ class Validator:
             out["latency"] = _copy_out(a.latency, a.n_arrays, np.int64)
             out["raw_op"] = _copy_out(a.raw_op, a.n_raw, np.uint32)
             out["raw_off"] = _copy_out(a.raw_off, nf * 4 + 1, np.uint32)
+        return out
+
+    @staticmethod
+    def _keyed_cols(cols, key, nkeys: int, names: str):
+        """The row columns as contiguous arrays of one length, and the key
+        column (None: every row in key 0)."""
+        n = len(cols[0])
+        if any(a.ndim != 1 or len(a) != n for a in cols):
+            raise ValueError(f"{names} must be 1-d and of one length")
+        if key is not None:
+            key = np.ascontiguousarray(key, np.uint32)
+            if key.ndim != 1 or len(key) != n:
+                raise ValueError("key must be 1-d and as long as the rows")
+        return n, key
+
+    def counter_check(self, type, f, process, value, key=None, nkeys: int = 1) -> dict:
+        """The reference's checker/counter per independent key over one row
+        per op in history order (hsc_counter_check; include/hip_serial.h has
+        the contract): ``type`` OP_INVOKE / OP_OK / OP_FAIL / OP_INFO, ``f``
+        CNT_ADD / CNT_READ / CNT_OTHER, ``process`` an id, ``value`` int64 with
+        CNT_NIL for nil, ``key`` below ``nkeys`` (None: one key).  Returns
+        copies of the report: ``nkeys``, ``bad``, ``unknown``, ``reads``,
+        ``bad_reads``, ``n_listed``, ``sort_packed``, ``ms``; per key
+        ``verdict`` (CNT_OK / CNT_BAD / CNT_UNKNOWN), ``malformed_op`` (NO_ROW:
+        none), ``malformed_kind``, ``errors`` and ``read_off`` [nkeys + 1];
+        per read ``lower``, ``value``, ``upper``, ``read_op``; and
+        ``listed_read``, the first COUNTER_LIST_CAP error reads."""
+        cols = [np.ascontiguousarray(a, t) for a, t in ((type, np.uint8), (f, np.uint8), (process, np.uint32),
+                                                        (value, np.int64))]
+        n, key = self._keyed_cols(cols, key, nkeys, "type, f, process and value")
+        s = _CounterIn(n, *(a.ctypes.data for a in cols), None if key is None else key.ctypes.data, nkeys)
+        a = CounterReport()
+        self._chk(self.lib.hsc_counter_check(self.ctx, C.byref(s), C.byref(a)), "hsc_counter_check")
+        out = {k: getattr(a, k) for k in ("nkeys", "bad", "unknown", "reads", "bad_reads", "n_listed", "sort_packed",
+                                          "ms")}
+        out["verdict"] = _copy_out(a.verdict, nkeys, np.uint8)
+        out["malformed_op"] = _copy_out(a.malformed_op, nkeys, np.uint32)
+        out["malformed_kind"] = _copy_out(a.malformed_kind, nkeys, np.uint8)
+        out["errors"] = _copy_out(a.errors, nkeys, np.uint32)
+        out["read_off"] = _copy_out(a.read_off, nkeys + 1, np.uint32)
+        for k in ("lower", "value", "upper"):
+            out[k] = _copy_out(getattr(a, k), a.reads, np.int64)
+        out["read_op"] = _copy_out(a.read_op, a.reads, np.uint32)
+        out["listed_read"] = _copy_out(a.listed_read, a.n_listed, np.uint32)
+        return out
+
+    def queue_check(self, f, value, key=None, nkeys: int = 1, fifo: bool = False, final: bool = False) -> dict:
+        """The reference's checker/queue per independent key over the rows it
+        selects, in history order (hsc_queue_check): ``f`` Q_ENQUEUE (every
+        ``:invoke :enqueue``) / Q_DEQUEUE (every ``:ok :dequeue``), ``value``
+        int64, ``key`` below ``nkeys`` (None: one key).  ``fifo``: the
+        fifo-queue model, else unordered-queue; ``final``: also the final
+        queues.  Returns copies of the report: ``nkeys``, ``bad``, ``n_final``,
+        ``sort_packed``, ``ms``; per key ``verdict`` (CNT_OK / CNT_BAD),
+        ``error_row`` (NO_ROW: none), ``error_kind`` (1 absent or mismatch, 2
+        empty), ``final_len`` and ``final_off`` [nkeys + 1]; ``final_val`` /
+        ``final_mult`` [n_final]."""
+        cols = [np.ascontiguousarray(f, np.uint8), np.ascontiguousarray(value, np.int64)]
+        n, key = self._keyed_cols(cols, key, nkeys, "f and value")
+        s = _QueueIn(n, *(a.ctypes.data for a in cols), None if key is None else key.ctypes.data, nkeys)
+        a = QueueReport()
+        flags = (QUEUE_FIFO if fifo else 0) | (QUEUE_FINAL if final else 0)
+        self._chk(self.lib.hsc_queue_check(self.ctx, C.byref(s), flags, C.byref(a)), "hsc_queue_check")
+        out = {k: getattr(a, k) for k in ("nkeys", "bad", "n_final", "sort_packed", "ms")}
+        out["verdict"] = _copy_out(a.verdict, nkeys, np.uint8)
+        out["error_row"] = _copy_out(a.error_row, nkeys, np.uint32)
+        out["error_kind"] = _copy_out(a.error_kind, nkeys, np.uint8)
+        out["final_len"] = _copy_out(a.final_len, nkeys, np.uint32)
+        out["final_off"] = _copy_out(a.final_off, nkeys + 1, np.uint32)
+        out["final_val"] = _copy_out(a.final_val, a.n_final, np.int64)
+        out["final_mult"] = _copy_out(a.final_mult, a.n_final, np.uint32)
         return out
 
     def probe_device(self, batch: ProbeBatch) -> None:

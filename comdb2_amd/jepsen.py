@@ -109,6 +109,7 @@ checkers of this module.
 """
 from __future__ import annotations
 
+import collections
 import dataclasses
 import decimal
 import fractions
@@ -1632,6 +1633,177 @@ def compose_bank(n: int, total: int) -> dict:
 
 
 # ---------------------------------------------------------------------------
+# the counter and queue checkers, per independent key
+# ---------------------------------------------------------------------------
+CNT_NIL = -(1 << 63)                              # HSC_CNT_NIL
+_CNT_F = {":add": 0, ":read": 1}                  # HSC_CNT_ADD, HSC_CNT_READ; anything else HSC_CNT_OTHER
+_CNT_VALID = {0: True, 1: False, 2: "unknown"}    # HSC_CNT_OK / _BAD / _UNKNOWN
+_CNT_KINDS = {1: "the process already has an op running", 2: "a completion without a prior invocation",
+              3: "the failure's value differs from its invocation's",
+              4: "the completion's :f differs from its invocation's",
+              5: "a nil value where the counter needs a number"}
+
+
+@dataclasses.dataclass
+class KeyedRows:
+    """Rows of a history as ``Validator.counter_check`` / ``queue_check`` take
+    them.  ``keys``: key index -> the history's key (None: the single
+    subhistory); ``ops``: per row its op as parsed."""
+    nkeys: int
+    key: np.ndarray
+    f: np.ndarray
+    value: np.ndarray
+    keys: List[object]
+    ops: List[dict]
+    type: Optional[np.ndarray] = None
+    process: Optional[np.ndarray] = None
+
+
+def _unwrap(op: dict, i: int, independent: bool):
+    """(key, value, keep) of an op: with ``independent`` the ``[k v]`` tuple of
+    independent/tuple unwrapped as :func:`lin_ops_from_register_edn` does.  The
+    reference puts an un-keyed op into every subhistory
+    (jepsen/independent.clj:239-250); an ``:info`` one changes nothing in
+    either checker and is dropped, any other is a ValueError."""
+    v = op.get(":value")
+    if not independent:
+        return None, v, True
+    if isinstance(v, list) and len(v) == 2:
+        k = v[0]
+        return (tuple(k) if isinstance(k, list) else k), v[1], True
+    if op.get(":type") == ":info":
+        return None, None, False
+    raise ValueError(f"op {i}: an un-keyed op in an independent history: {op!r}")
+
+
+def counter_ops_from_edn(text: str, independent: bool = False) -> KeyedRows:
+    """Every op map of a counter history as a row: ``:type``, ``:f`` (``:add``
+    / ``:read`` / other), ``:process`` interned, ``:value`` (nil -> CNT_NIL; a
+    value of an other-f op that is no integer is interned too: only its
+    equality with its invocation's matters)."""
+    key_ix: Dict[object, int] = {}
+    pid: Dict[object, int] = {}
+    odd: Dict[str, int] = {}
+    key, typ, f, proc, val, ops = [], [], [], [], [], []
+    for i, op in enumerate(o for o in _flatten(parse_edn(text)) if isinstance(o, dict)):
+        if op.get(":type") not in PERF_TYPES:
+            raise ValueError(f"op {i}: :type {op.get(':type')!r}")
+        k, v, keep = _unwrap(op, i, independent)
+        if not keep:
+            continue
+        fk = _CNT_F.get(op.get(":f"), 2)
+        if v is None:
+            v = CNT_NIL
+        elif fk == 2 and type(v) is not int:
+            v = (1 << 62) + odd.setdefault(repr(v), len(odd))
+        else:
+            v = _int_value(v, "counter")
+        p = op.get(":process")
+        key.append(key_ix.setdefault(k, len(key_ix)))
+        typ.append(PERF_TYPES.index(op[":type"]))
+        f.append(fk)
+        proc.append(pid.setdefault((type(p), repr(p)), len(pid)))
+        val.append(v)
+        ops.append(op)
+    return KeyedRows(max(len(key_ix), 1), np.array(key, np.uint32), np.array(f, np.uint8), np.array(val, np.int64),
+                     list(key_ix) or [None], ops, np.array(typ, np.uint8), np.array(proc, np.uint32))
+
+
+def _independent(rows: KeyedRows, reports: List[dict], independent: bool) -> dict:
+    """One report, or independent/checker's map of them
+    (jepsen/independent.clj:252-290)."""
+    if not independent:
+        return reports[0]
+    results = {} if rows.keys == [None] and not rows.ops else dict(zip(rows.keys, reports))
+    return {"valid": merge_valid(r["valid"] for r in results.values()) if results else True, "results": results,
+            "failures": [k for k, r in results.items() if r["valid"] is not True]}
+
+
+def counter_report(rows: KeyedRows, res: dict, independent: bool = False) -> dict:
+    """checker/counter's map per key from a ``Validator.counter_check`` dict (a
+    pure function): {"valid", "reads": [[lower, value, upper], ...],
+    "errors": [...]}, or {"valid": "unknown", "error": ...} naming the op of a
+    malformed history (the reference throws there; check-safe answers
+    :unknown)."""
+    reports = []
+    for k in range(rows.nkeys):
+        if res["verdict"][k] == 2:
+            o, kind = int(res["malformed_op"][k]), int(res["malformed_kind"][k])
+            reports.append({"valid": "unknown", "op": rows.ops[o], "op_index": o, "kind": kind,
+                            "error": f"malformed history at op {o} ({_CNT_KINDS[kind]}): {rows.ops[o]!r}"})
+            continue
+        a, b = int(res["read_off"][k]), int(res["read_off"][k + 1])
+        reads = [[int(lo), int(v), int(hi)] for lo, v, hi in
+                 zip(res["lower"][a:b], res["value"][a:b], res["upper"][a:b])]
+        reports.append({"valid": _CNT_VALID[int(res["verdict"][k])], "reads": reads,
+                        "errors": [r for r in reads if not r[0] <= r[1] <= r[2]]})
+    return _independent(rows, reports, independent)
+
+
+def check_counter_edn(validator, text: str, independent: bool = False) -> dict:
+    """checker/counter (jepsen/checker.clj:220-272) through the GPU --
+    wrapped in independent/checker with ``independent`` --
+    :func:`counter_ops_from_edn`, ``Validator.counter_check``,
+    :func:`counter_report`."""
+    rows = counter_ops_from_edn(text, independent)
+    res = validator.counter_check(rows.type, rows.f, rows.process, rows.value, rows.key, rows.nkeys)
+    return counter_report(rows, res, independent)
+
+
+def queue_rows_from_edn(text: str, independent: bool = False) -> KeyedRows:
+    """The rows checker/queue selects (jepsen/checker.clj:95-100), in history
+    order: every ``:invoke :enqueue`` and every ``:ok :dequeue``."""
+    key_ix: Dict[object, int] = {}
+    key, f, val, ops = [], [], [], []
+    for i, op in enumerate(o for o in _flatten(parse_edn(text)) if isinstance(o, dict)):
+        k, v, keep = _unwrap(op, i, independent)
+        if not keep:
+            continue
+        tf = (op.get(":type"), op.get(":f"))
+        if independent:
+            key_ix.setdefault(k, len(key_ix))  # (a key with no selected row still has a subhistory)
+        if tf not in ((":invoke", ":enqueue"), (":ok", ":dequeue")):
+            continue
+        key.append(key_ix.setdefault(k, len(key_ix)))
+        f.append(0 if tf[1] == ":enqueue" else 1)
+        val.append(_int_value(v, tf[1][1:]))
+        ops.append(op)
+    return KeyedRows(max(len(key_ix), 1), np.array(key, np.uint32), np.array(f, np.uint8), np.array(val, np.int64),
+                     list(key_ix) or [None], ops)
+
+
+def queue_report(rows: KeyedRows, res: dict, fifo: bool, independent: bool = False) -> dict:
+    """checker/queue's map per key from a ``Validator.queue_check(final=True)``
+    dict (a pure function): {"valid": True, "final_queue": ...} -- unordered:
+    the remaining (value, multiplicity) pairs ascending; fifo: the remaining
+    values in queue order -- or {"valid": False, "error": msg} with the
+    model's message (jepsen/model.clj:80, :93-100)."""
+    reports = []
+    for k in range(rows.nkeys):
+        if res["verdict"][k]:
+            r = int(res["error_row"][k])
+            msg = f"can't dequeue {int(rows.value[r])}" + (" from empty queue" if res["error_kind"][k] == 2 else "")
+            reports.append({"valid": False, "error": msg, "op": rows.ops[r]})
+            continue
+        a, b = int(res["final_off"][k]), int(res["final_off"][k + 1])
+        vals = [int(v) for v in res["final_val"][a:b]]
+        reports.append({"valid": True, "final_queue": vals if fifo else
+                        list(zip(vals, (int(m) for m in res["final_mult"][a:b])))})
+    return _independent(rows, reports, independent)
+
+
+def check_queue_edn(validator, text: str, model: str = "unordered", independent: bool = False) -> dict:
+    """checker/queue (jepsen/checker.clj:87-106) through the GPU with the
+    ``model`` "unordered" (model/unordered-queue) or "fifo" (model/fifo-queue),
+    wrapped in independent/checker with ``independent``."""
+    if model not in ("unordered", "fifo"):
+        raise ValueError(f"model: {model!r}")
+    rows = queue_rows_from_edn(text, independent)
+    res = validator.queue_check(rows.f, rows.value, rows.key, rows.nkeys, fifo=model == "fifo", final=True)
+    return queue_report(rows, res, model == "fifo", independent)
+
+
+# ---------------------------------------------------------------------------
 # generated histories (test inputs; the reference's clients need a live
 # cluster and a JVM)
 # ---------------------------------------------------------------------------
@@ -2176,3 +2348,112 @@ def bank_history_edn(seed: int, n: int = 5, start: int = 10, n_ops: int = 500, n
             bal[dst] += amount
             lines.append(f"{{:type :ok, :f :transfer, :value {val}, :process {p}}}")
     return "\n".join(lines) + "\n", {"skewed": skewed, "short": short}
+
+
+def _kv(n_keys: int, k: int, v) -> str:
+    v = "nil" if v is None else str(v)
+    return f"[{k} {v}]" if n_keys else v
+
+
+def counter_history_edn(seed: int, n_ops: int = 400, n_procs: int = 5, n_keys: int = 0, fail: float = 0.05,
+                        info: float = 0.05, bad_reads: int = 0, malformed: int = 0) -> Tuple[str, dict]:
+    """A counter history: adds of 1 .. 5 and reads by n_procs processes, one
+    op in flight per process, executed against a real counter at completion
+    (an ``:ok`` add counts, a ``:fail`` one does not, an ``:info`` one may, and
+    retires its process).  ``n_keys`` > 0: that many independent counters, the
+    values ``[k v]`` tuples.  ``bad_reads`` reads return one more than every
+    add attempted so far could give; ``malformed`` ops complete twice.
+    Returns (EDN text, {"bad": the keys with such a read, "malformed": the
+    keys with such an op}; key 0 stands for the single counter)."""
+    rng = np.random.default_rng(seed)
+    nk = max(n_keys, 1)
+    is_add = rng.random(n_ops) < 0.5
+    amount = rng.integers(1, 6, n_ops)
+    okey = rng.integers(0, nk, n_ops)
+    fate = rng.choice(3, n_ops, p=[1 - fail - info, fail, info])  # ok, fail, info
+    reads = np.flatnonzero(~is_add & (fate == 0))
+    bad_at = set(rng.choice(reads, min(bad_reads, len(reads)), replace=False).tolist()) if bad_reads else set()
+    twice = set(rng.choice(n_ops, min(malformed, n_ops), replace=False).tolist()) if malformed else set()
+    actual, upper, gen = [0] * nk, [0] * nk, [0] * n_procs
+    inj = {"bad": set(), "malformed": set()}
+
+    def pid(p):
+        return p + n_procs * gen[p]
+
+    def invoke(i, p):
+        k = int(okey[i])
+        if is_add[i]:
+            upper[k] += int(amount[i])
+            return f"{{:type :invoke, :f :add, :value {_kv(n_keys, k, int(amount[i]))}, :process {pid(p)}}}"
+        return f"{{:type :invoke, :f :read, :value {_kv(n_keys, k, None)}, :process {pid(p)}}}"
+
+    def complete(i, p):
+        k, t, me = int(okey[i]), (":ok", ":fail", ":info")[fate[i]], pid(p)
+        if is_add[i]:
+            if fate[i] == 0 or (fate[i] == 2 and rng.random() < 0.5):
+                actual[k] += int(amount[i])
+            v = int(amount[i])
+        else:
+            v = None if fate[i] else upper[k] + 1 if i in bad_at else actual[k]
+            if i in bad_at:
+                inj["bad"].add(k)
+        if fate[i] == 2:
+            gen[p] += 1
+        line = f"{{:type {t}, :f {':add' if is_add[i] else ':read'}, :value {_kv(n_keys, k, v)}, :process {me}}}"
+        if i in twice and fate[i] != 2:
+            inj["malformed"].add(k)
+            return line + "\n" + line
+        return line
+
+    lines = _interleave(rng, n_procs, n_ops, invoke, complete)
+    return "\n".join(lines) + "\n", {k: sorted(v) for k, v in inj.items()}
+
+
+def fifo_queue_history_edn(seed: int, n_ops: int = 400, n_procs: int = 5, n_keys: int = 0, swap: int = 0,
+                           phantom: int = 0, fail_enq: float = 0.05) -> Tuple[str, dict]:
+    """A queue history that both of checker/queue's models accept: enqueues of
+    distinct values (in the queue from their invocation, ``fail_enq`` of them
+    completing ``:fail``, as the checker counts them) and dequeues that take
+    the head of a real FIFO queue at completion (``:fail`` on an empty one).
+    ``n_keys`` > 0: independent queues, ``[k v]`` values.  ``swap`` dequeues
+    take the second element instead (illegal for fifo-queue only),
+    ``phantom`` dequeues return a value nobody enqueued (illegal for both).
+    Returns (EDN text, {"swapped": keys, "phantom": keys})."""
+    rng = np.random.default_rng(seed)
+    nk = max(n_keys, 1)
+    is_enq = rng.random(n_ops) < 0.55
+    okey = rng.integers(0, nk, n_ops)
+    failed = rng.random(n_ops) < fail_enq
+    deqs = np.flatnonzero(~is_enq)
+    picks = rng.permutation(deqs)[:swap + phantom].tolist()
+    swap_at, phantom_at = set(picks[:swap]), set(picks[swap:])
+    queues = [collections.deque() for _ in range(nk)]
+    inj = {"swapped": set(), "phantom": set()}
+
+    def invoke(i, p):
+        k = int(okey[i])
+        if is_enq[i]:
+            queues[k].append(i)
+            return f"{{:type :invoke, :f :enqueue, :value {_kv(n_keys, k, i)}, :process {p}}}"
+        return f"{{:type :invoke, :f :dequeue, :value {_kv(n_keys, k, None)}, :process {p}}}"
+
+    def complete(i, p):
+        k, q = int(okey[i]), queues[int(okey[i])]
+        if is_enq[i]:
+            t = ":fail" if failed[i] else ":ok"
+            return f"{{:type {t}, :f :enqueue, :value {_kv(n_keys, k, i)}, :process {p}}}"
+        if i in phantom_at:
+            inj["phantom"].add(k)
+            v = 10 ** 6 + i
+        elif not q:
+            return f"{{:type :fail, :f :dequeue, :value {_kv(n_keys, k, None)}, :process {p}}}"
+        elif i in swap_at and len(q) >= 2:
+            inj["swapped"].add(k)
+            v = q[1]
+            del q[1]
+        else:
+            v = q.popleft()
+        return f"{{:type :ok, :f :dequeue, :value {_kv(n_keys, k, v)}, :process {p}}}"
+
+    lines = _interleave(rng, n_procs, n_ops, invoke, complete)
+    return "\n".join(lines) + "\n", {k: sorted(v) for k, v in inj.items()}

@@ -1523,6 +1523,136 @@ typedef struct hsc_perf_report {
     float phase_ms[HSC_PERF_NPHASE]; /* of it: upload + rows, pairing, latency cells, rate, raw partition */
 } hsc_perf_report;
 int hsc_perf_check(hsc_ctx *ctx, const hsc_perf_in *in, unsigned flags, hsc_perf_report *out);
+
+/* ---- the counter and queue checkers, per independent key ---------------------
+ * checker/counter (jepsen/checker.clj:220-272) and checker/queue (:87-106), the
+ * two members of checker.clj that are sequential reductions, each judged for
+ * many keys in one call: what independent/checker (jepsen/independent.clj:
+ * 252-290) wraps around them.  key[i] < nkeys names the row's subhistory; key
+ * may be NULL when nkeys is 1.  Keys are judged independently and reported per
+ * key; a key without rows is ok.  DESIGN.md §5m.
+ * hsc_counter_check takes one row per op in history order: type (HSC_OP_*), f
+ * (HSC_CNT_ADD / _READ / _OTHER), process (an id) and value, HSC_CNT_NIL
+ * standing for nil.  Per key it is history/complete (knossos/history.clj:
+ * 87-171) followed by the checker's loop (checker.clj:240-272).
+ * Completion: a process's rows of one key without the :info rows must
+ * alternate invoke, ok or fail, invoke, ...  A row is malformed, by kind:
+ *   1  an invoke whose predecessor in that sequence is an invoke (history.clj:
+ *      101-106 throws)
+ *   2  an ok or fail whose predecessor is no invoke, or that has none (:114,
+ *      :128)
+ *   3  a fail whose value differs from its invoke's (:132)
+ *   4  a completion whose f differs from its invoke's.  The reference does not
+ *      check this and would build a nonsense triple from the two; here the row
+ *      is malformed
+ *   5  an add invoke, an ok add or an ok read whose effective value is nil
+ *      (the loop's + and <= throw on it)
+ * (a row of several kinds reports the smallest).  A key with a malformed row
+ * has verdict HSC_CNT_UNKNOWN -- the reference throws and checker/check-safe
+ * answers :unknown -- malformed_op[k] is the smallest such op index,
+ * malformed_kind[k] that row's kind, and the key lists no reads.  Other keys:
+ * malformed_op ~0u, kind 0.
+ * Effective value: an invoke completed by an ok takes the completion's value
+ * (history.clj:117-119); every other invoke keeps its own.
+ * Bounds: upper after row i = the sum of the effective values of the key's add
+ * invokes at or before i, those that later fail or end in :info included (the
+ * reference never looks at :fails?); lower after row i = the sum of the values
+ * of its ok adds at or before i.  Both wrap in 64 bits, as hsc_bank_check's
+ * sums do, where the reference's + would throw on overflow.
+ * Reads: every ok read at row j with its invoke at row i yields the triple
+ * (lower after i, value[j], upper after j), listed per key in order of j:
+ * key k's reads are [read_off[k], read_off[k + 1]) of lower / value / upper /
+ * read_op (read_op = j).  A triple is an error unless lower <= value <= upper
+ * (signed; both bounds inclusive).  errors[k] and bad_reads are exact; the
+ * first n_listed = min(bad_reads, HSC_COUNTER_LIST_CAP) error reads are listed
+ * as ascending indices into the read arrays.  Verdict HSC_CNT_BAD: a key with
+ * an error read.  :max-absolute-error / :max-relative-error are named by the
+ * reference's docstring and computed nowhere; nor here.
+ * HSC_EINVAL: a NULL argument (an array may be NULL when n is 0, key when
+ * nkeys is 1), nkeys of 0, a key >= nkeys, a type above HSC_OP_INFO, an f above
+ * HSC_CNT_OTHER, or n > 0x7FFFFFFF -- all found on the host before any launch.
+ * HSC_EDEVICE: a host-only context.  n == 0 succeeds with every key ok.  The
+ * arrays are host memory owned by the context, never NULL, valid until the
+ * next hsc_counter_check on it.  Nothing another entry left on the context is
+ * touched: the sorts have rows of their own. */
+#define HSC_COUNTER_LIST_CAP 4096
+#define HSC_CNT_NIL INT64_MIN
+enum { HSC_CNT_ADD, HSC_CNT_READ, HSC_CNT_OTHER };
+enum { HSC_CNT_OK, HSC_CNT_BAD, HSC_CNT_UNKNOWN };  /* a key's verdict, both entries */
+typedef struct hsc_counter_in {
+    size_t n;
+    const uint8_t *type;           /* [n] HSC_OP_* */
+    const uint8_t *f;              /* [n] HSC_CNT_* */
+    const uint32_t *process;       /* [n] */
+    const int64_t *value;          /* [n] */
+    const uint32_t *key;           /* [n] below nkeys; NULL: all 0 (nkeys == 1) */
+    uint32_t nkeys;
+} hsc_counter_in;
+typedef struct hsc_counter_report {
+    uint32_t nkeys;
+    uint32_t bad, unknown;         /* keys by verdict */
+    const uint8_t *verdict;        /* [nkeys] */
+    const uint32_t *malformed_op;  /* [nkeys] ~0u: none */
+    const uint8_t *malformed_kind; /* [nkeys] */
+    const uint32_t *read_off;      /* [nkeys + 1] */
+    uint64_t reads, bad_reads;
+    const int64_t *lower, *value, *upper;  /* [reads] */
+    const uint32_t *read_op;       /* [reads] the ok read's op index */
+    const uint32_t *errors;        /* [nkeys] error reads of the key */
+    uint32_t n_listed;
+    const uint32_t *listed_read;   /* [n_listed] ascending */
+    int sort_packed;               /* bit 0: the pairing sort ran as packed single words, 1: the key sort */
+    float ms;                      /* device time of the whole call */
+} hsc_counter_report;
+int hsc_counter_check(hsc_ctx *ctx, const hsc_counter_in *in, hsc_counter_report *out);
+/* hsc_queue_check takes only the rows checker/queue selects (checker.clj:
+ * 95-100), in history order: every :invoke :enqueue, whatever became of it (a
+ * failed enqueue is in the queue, as in the reference), and every :ok :dequeue;
+ * per row f (HSC_Q_ENQUEUE / _DEQUEUE), value and key.  Per key it computes
+ * (reduce model/step model rows) for jepsen/model.clj's unordered-queue
+ * (:73-85) or, with HSC_QUEUE_FIFO, fifo-queue (:87-105).  Inconsistent absorbs
+ * every later step, so a key's error is its first illegal dequeue in history
+ * order: error_row[k] (an index into the rows, ~0u: none) and error_kind[k]:
+ *   1  unordered: the value's pending count is 0; fifo: the queue's head is
+ *      another value -- "can't dequeue V"
+ *   2  fifo: the queue is empty -- "can't dequeue V from empty queue" (checked
+ *      first, as the model's cond does)
+ * final_len[k]: the elements left, 0 for a bad key.  With HSC_QUEUE_FINAL the
+ * final queues too: key k's at [final_off[k], final_off[k + 1]) of final_val /
+ * final_mult -- unordered: the distinct remaining values ascending (signed)
+ * with their multiplicity; fifo: the remaining values in queue order,
+ * multiplicity 1.  No cap: a final queue is at most the enqueues.  Without the
+ * flag the two arrays are empty and final_off is all zero.
+ * HSC_EINVAL: a NULL argument (an array may be NULL when n is 0, key when
+ * nkeys is 1), nkeys of 0, a key >= nkeys, an f above HSC_Q_DEQUEUE, a flag
+ * other than the two, or n > 0x7FFFFFFF -- found on the host before any
+ * launch.  HSC_EDEVICE: a host-only context.  n == 0 succeeds with every key
+ * ok.  Ownership as hsc_counter_check: valid until the next hsc_queue_check. */
+#define HSC_QUEUE_FIFO 1u
+#define HSC_QUEUE_FINAL 2u
+enum { HSC_Q_ENQUEUE, HSC_Q_DEQUEUE };
+typedef struct hsc_queue_in {
+    size_t n;
+    const uint8_t *f;              /* [n] HSC_Q_* */
+    const int64_t *value;          /* [n] */
+    const uint32_t *key;           /* [n] below nkeys; NULL: all 0 (nkeys == 1) */
+    uint32_t nkeys;
+} hsc_queue_in;
+typedef struct hsc_queue_report {
+    uint32_t nkeys;
+    uint32_t bad;                  /* keys with an error */
+    const uint8_t *verdict;        /* [nkeys] HSC_CNT_OK / HSC_CNT_BAD */
+    const uint32_t *error_row;     /* [nkeys] ~0u: none */
+    const uint8_t *error_kind;     /* [nkeys] 0 none, 1 absent / mismatch, 2 empty */
+    const uint32_t *final_len;     /* [nkeys] */
+    const uint32_t *final_off;     /* [nkeys + 1] */
+    uint64_t n_final;              /* final_off[nkeys] */
+    const int64_t *final_val;      /* [n_final] */
+    const uint32_t *final_mult;    /* [n_final] */
+    int sort_packed;               /* the entry's sort ran as packed single words */
+    float ms;                      /* device time of the whole call */
+} hsc_queue_report;
+int hsc_queue_check(hsc_ctx *ctx, const hsc_queue_in *in, unsigned flags, hsc_queue_report *out);
 /* cover_dev[ntxn of the last build] := 1 inside a backward edge's interval. */
 int hsc_dep_graph_cover(hsc_ctx *ctx, uint8_t *cover_dev);
 /* Edges of the last build with both ends covered, as rows src << 32 | dst
